@@ -20,6 +20,11 @@ time).  Launch: `python bench.py` (1 GPU) or torch.distributed.run with
 exchange of SURVEY.md 8(e)); its time is reported separately, not in value.
 `--backend gloo` rehearses the N > 1 path (barrier, max-over-ranks timing,
 gather) with several ranks sharing one GPU; bench numbers use nccl (RCCL).
+
+A plain run sets up, warms up, times the steps and prints the line.  `--full`
+adds the measurements that take runs of their own (the fp64 CPU restatement
+behind `cpu_baseline`, tens of seconds on 16 cores).  `--dump-outputs DIR`
+writes what the last timed step left in the solver (dump_outputs).
 """
 from __future__ import annotations
 
@@ -352,6 +357,34 @@ def cpu_baseline(geo, stack_host, threads, cores_note):
                        f"single core: 1 patch x {geo['n_led']} LEDs, {dt1:.1f} s")
 
 
+DUMP_SEED = 20261015
+DUMP_BYTES = {"objCrop": 24_000_000, "objF": 20_000_000, "pupil": 16_000_000}  # 60 MB in all
+
+
+def dump_outputs(solver, out_dir):
+    """Write the solver's state after the last timed step -- what a caller of
+    fpm_download receives: objCrop (the reconstructed patches), objF (their
+    spectra) and pupil, each complex64 [patch][y][x] -- as out_dir/<name>.npy,
+    float32 with a trailing (re, im) axis.  An array above its share of the
+    60 MB budget (DUMP_BYTES) is written as a fixed sample instead: shape
+    [k][2], the complex elements at the sorted flat indices
+    numpy.random.default_rng(DUMP_SEED).integers(0, array.size, k), the same
+    elements in every run of the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    solver.synchronize()
+    got = solver.download(support=False)
+    for name, cap in DUMP_BYTES.items():
+        a = got[name].reshape(-1)
+        if a.nbytes > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, a.size, cap // 8))
+            a = a[idx]
+            out = a.view(np.float32).reshape(-1, 2)
+        else:
+            out = got[name].view(np.float32).reshape(got[name].shape + (2,))
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(out, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -372,7 +405,12 @@ def main():
     ap.add_argument("--fp16", action="store_true", help="fp16 spectrum storage (default for --config c5)")
     ap.add_argument("--path", default="auto", choices=["auto", "general", "fused"])
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every core this job may use (host_cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the fp64 CPU restatement (cpu_baseline)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU restatement")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write rank 0's objCrop, objF and pupil (or a fixed seeded sample "
+                         "of each, 60 MB in all) to DIR/<name>.npy as float32 (dump_outputs)")
     ap.add_argument("--no-gather", action="store_true")
     ap.add_argument("--pmc", default="", help="counter profile (tools/pmc_to_json.py); default: the workload's "
                                               "profiles/pmc_<config>_<kernel>.json")
@@ -513,6 +551,8 @@ def main():
                           "(100 MHz) at entry and after its last LED; a slow box reads as a lower clock at the "
                           "same cycles (fpm_get_clock)")
     roofline = roofline_line(geo, info, per_launch_ms, per_launch_updates, args.pmc or default_pmc(args, info), clock)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(solver, args.dump_outputs)
 
     gather = None
     if world > 1 and not args.no_gather:
@@ -564,7 +604,7 @@ def main():
                       led_updates_per_s_incl_upload_1_iteration=round(B * geo["n_led"] / (us + elapsed / args.steps), 1))
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "metric":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "metric":
         cores, note = host_cores()
         threads = args.cpu_threads or min(cores, B)
         host_stack = stack[:, :threads].contiguous().cpu().numpy().view(np.uint16)

@@ -40,6 +40,77 @@ def test_gpus_mismatch_under_launcher_refuses(monkeypatch):
     assert calls == [] and "WORLD_SIZE=2" in str(code)
 
 
+class _FakeSolver:
+    """download() of a 3-patch context, filled with known values."""
+
+    def __init__(self):
+        import numpy as np
+        rng = np.random.default_rng(7)
+
+        def c(*shape):
+            return (rng.standard_normal(shape) + 1j * rng.standard_normal(shape)).astype(np.complex64)
+        self.out = dict(objF=c(3, 24, 24), objCrop=c(3, 24, 24), pupil=c(3, 8, 8), support=None)
+
+    def synchronize(self):
+        pass
+
+    def download(self, **kw):
+        assert kw == {"support": False}
+        return self.out
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: an array within its byte share is written whole as
+    float32 [..., 2]; a larger one as the seeded sample of its elements, the
+    same elements on every call."""
+    import numpy as np
+    import bench
+    s = _FakeSolver()
+    monkeypatch.setattr(bench, "DUMP_BYTES", {"objCrop": 8 * 100, "objF": 10 ** 6, "pupil": 10 ** 6})
+    bench.dump_outputs(s, str(tmp_path / "a"))
+    bench.dump_outputs(s, str(tmp_path / "b"))
+    for name in ("objCrop", "objF", "pupil"):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy"))
+        full = s.out[name]
+        if name == "objCrop":
+            idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, full.size, 100))
+            assert a.shape == (100, 2) and np.array_equal(a[:, 0] + 1j * a[:, 1], full.reshape(-1)[idx])
+        else:
+            assert a.shape == full.shape + (2,) and np.array_equal(a[..., 0] + 1j * a[..., 1], full)
+
+
+def test_dump_budget():
+    """The dumped arrays stay within 64 MB in all."""
+    import bench
+    assert sum(bench.DUMP_BYTES.values()) <= 64 * 10 ** 6
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_repeatable_outputs(tmp_path, monkeypatch, capsys):
+    """A plain run (2 patches of config 2) times exactly --steps steps, leaves
+    cpu_baseline out, and two runs with the same arguments dump identical
+    arrays: the seeded inputs and the solver are deterministic."""
+    import json
+    import numpy as np
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    lines = []
+    for d in ("a", "b"):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--config", "c2",
+                                          "--patches", "2", "--dump-outputs", str(tmp_path / d)])
+        bench.main()
+        lines.append(json.loads(capsys.readouterr().out.strip().splitlines()[-1]))
+    for ln in lines:
+        assert ln["steps"] == 2 and ln["ms_per_step"] > 0 and ln["cpu_baseline"] is None
+        assert ln["value"] == pytest.approx(2 * 193 / (ln["ms_per_step"] * 1e-3), rel=5e-3)
+    for name, shape in (("objCrop", (2, 360, 360, 2)), ("objF", (2, 360, 360, 2)), ("pupil", (2, 90, 90, 2))):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all() and np.abs(a).max() > 0
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy"))
+
+
 def test_general_path_traffic_counts_every_patch_group(tmp_path):
     """The general path runs each per-LED kernel once per patch group, so a
     counter file's per-dispatch bytes cover one group: bench.load_pmc scales
