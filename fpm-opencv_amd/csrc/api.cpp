@@ -23,62 +23,10 @@
 #include "../../include/fpm_hip_debug.h"
 #include "fft_lds.hpp"
 #include "fpm_state.hpp"
+#include "fused_sync.hpp"
+#include "launch.hpp"
 
 namespace fpm {
-hipError_t launch_general_step(const DevState &st, int led, int x0, int y0, const FftPlan &pl,
-                               const float2 *tw, bool first, hipStream_t s);
-hipError_t launch_pupil_commit(const DevState &st, hipStream_t s);
-int fft_max_len();
-int pupil_parts(int nb);
-hipError_t launch_init(const DevState &st, int init_led, float2 *scratch, const FftPlan &pl_np,
-                       const float2 *tw_np, hipStream_t s);
-hipError_t launch_objcrop(const DevState &st, float2 *out, const FftPlan &pl_L, const float2 *tw_L,
-                          hipStream_t s);
-// fused path (fpm_fused.hip)
-int fused_threads(int np, int r, int L, const DevState &st);
-// Np 200 fused kernel (fused_mr.hip)
-bool fused_mr_supported(int np, int r, const DevState &st);
-hipError_t launch_fused_mr_iteration(const DevState &st, const uint16_t *meas, const int *order_dev,
-                                     const int *x0_dev, const int *y0_dev, int n_order, const float2 *tw_np,
-                                     unsigned long long *dbg, hipStream_t s);
-// Np 90 fused kernel (fused_s90.hip)
-bool fused_s90_supported(int np, int r, const DevState &st);
-hipError_t launch_fused_s90_iteration(const DevState &st, const uint16_t *meas, const int *order_dev,
-                                      const int *x0_dev, const int *y0_dev, int n_order, const float2 *tw_np,
-                                      unsigned long long *dbg, hipStream_t s);
-// small-patch fused kernel (fused_small.hip, Np <= 96)
-bool fused_small_supported(int np, int r, const DevState &st);
-hipError_t launch_fused_small_iteration(const DevState &st, const uint16_t *meas, const int *order_dev,
-                                        const int *x0_dev, const int *y0_dev, int n_order, const float2 *tw_np,
-                                        const FftPlan &pl, unsigned long long *dbg, hipStream_t s);
-// Np 1024 / Np 256 register row/column kernels of the general path
-// (np1024.hip, np256.hip; both fold the pupil commit into the next LED)
-bool np1024_supported(int np, int r);
-bool np256_supported(int np, int r, int L, bool fp16);
-bool commit_folded(const DevState &st);
-hipError_t launch_fused_iteration(const DevState &st, const uint16_t *meas, const int *order_dev,
-                                  const int *x0_dev, const int *y0_dev, int n_order, const float2 *tw_np,
-                                  int ks, unsigned long long *dbg, float2 *xch, int *flags, int stall_led,
-                                  hipStream_t s);
-size_t fused_xch_elems(int B, int ks);
-size_t fused_flag_words(int B, int ks);
-int fused_split_parts(int nt, int B, int n_cu);
-// distributed mode of the Np 256 kernel (fused_dist.hip)
-size_t fused_dist_elems(int B, int ks);
-int fused_dist_parts(int B, int n_cu, int r, int L);
-hipError_t launch_fused_dist(const DevState &st, const uint16_t *meas, const int *order_dev, const int *x0_dev,
-                             const int *y0_dev, int n_order, const float2 *tw_np, int ks, unsigned long long *dbg,
-                             float2 *area, int *flags, int stall_led, unsigned tag_base, hipStream_t s);
-// in-place measurement layout of the fused kernels (preprocess.hip)
-hipError_t meas_layout(uint16_t *meas, int np, int g, size_t nimg, bool fwd, hipStream_t s);
-bool meas_layout_copy(const uint16_t *src, uint16_t *dst, int np, int g, size_t nimg, hipStream_t s,
-                      hipError_t *err);
-hipError_t launch_preprocess_frame(const uint16_t *frame, int width, int np, int B, const int *px0_dev,
-                                   const int *py0_dev, int bk1x, int bk1y, int bk2x, int bk2y, double bg_threshold,
-                                   double dark_mult, bool darkfield, unsigned long long *sums, uint16_t *out,
-                                   int16_t *bg_out_dev, hipStream_t s);
-size_t fused_T_elems(int np, int r, int B);
-
 // Co-resident grids (split / distributed modes, fused_sync.hpp): the
 // occupancy check, then a plain launch ordered after the previous co-resident
 // grid of this process on the same device (another context, another stream),
@@ -171,6 +119,32 @@ std::vector<float2> twiddles(int n) {
     return t;
 }
 
+// The LED-update kernel of a context, chosen once in fpm_create; kKernels has
+// one row per value, in this order.
+enum class Kernel { General, Np256, Np256Dist, Np200, Np90, Small };
+
+const char *const kStampsFused[kStamps] = {"gather", "A:tail+sync", "B:columns", "C:tail+sync", "upd:sync+Opre", "max",
+                                           "P",      "A:rowIDFT",   "C:rowDFT",  "upd:body",    "B:loop",
+                                           "split:Fstores", "split:Fwait"};
+const char *const kStampsDist[kStamps] = {"gather", "A", "sync1", "B", "sync2", "C", "update", "sync3",
+                                          "merge+Opre", "max", "P", "C:rows(sub)", "sync3:acks(sub)"};
+
+struct KernelRow {
+    int code;                   // fpm_info.fused_kernel (FPM_KERNEL_*)
+    int threads;                // per workgroup; 0 = the general path's several kernels
+    int meas_g;                 // lane-group size of the stack's column layout (meas_layout); -1 = Np
+                                // (transposed); the general path picks its own
+    const char *const *stamps;  // FPM_STAMPS phase names
+};
+constexpr KernelRow kKernels[] = {
+    {FPM_KERNEL_GENERAL, 0, 0, nullptr},                    // general.hip, np1024.hip, np256.hip
+    {FPM_KERNEL_FUSED_NP256, 512, 16, kStampsFused},        // fpm_fused.hip, one workgroup or split mode
+    {FPM_KERNEL_FUSED_NP256_DIST, 512, 16, kStampsDist},    // fused_dist.hip
+    {FPM_KERNEL_FUSED_NP200, 768, 10, kStampsFused},        // fused_mr.hip
+    {FPM_KERNEL_FUSED_NP90, 1024, 9, kStampsFused},         // fused_s90.hip
+    {FPM_KERNEL_FUSED_SMALL, 1024, -1, kStampsFused},       // fused_small.hip
+};
+
 }  // namespace
 
 struct fpm_ctx {
@@ -187,18 +161,15 @@ struct fpm_ctx {
     float2 *objcrop = nullptr;
     uint16_t *meas = nullptr;
     int meas_g = 0;                 // meas holds the column layout of meas_layout with g-lane groups
-                                    // once uploaded (16: Np 256, 10: Np 200, Np: the small-patch
-                                    // kernel and the Np 1024 general path, transposed); 0: C-ABI
-    int fused_nt = 0;               // Np 256 fused kernel: threads per workgroup (512), 0 = not used
+                                    // once uploaded (kKernels; Np: the Np 1024 general path,
+                                    // transposed); 0: C-ABI
+    Kernel kernel = Kernel::General;  // the LED-update kernel (General unless path is fused)
+    const KernelRow &row() const { return kKernels[(int)kernel]; }
     int split_ks = 1;               // split / distributed mode: workgroups per patch (2, 4, 8), else 1
-    bool dist = false;              // distributed mode (fused_dist.hip) instead of split mode
     float2 *xch = nullptr;          //   exchange area
     int *split_flags = nullptr;     //   handoff flags [KS B] + sticky abort flag + XCC ids [KS B]
     int stall_led = -1;             //   fpm_debug_set_stall (tests): the last part stops publishing
     unsigned dist_tags = 0;         //   distributed mode: LEDs launched so far (tile-word tags)
-    bool fused_mr = false;          // fused path runs the Np 200 kernel (fused_mr.hip)
-    bool fused_small = false;       // fused path runs the small-patch kernel (fused_small.hip)
-    bool fused_s90 = false;         // fused path runs the Np 90 kernel (fused_s90.hip)
     int *order_dev = nullptr, *x0_dev = nullptr, *y0_dev = nullptr;
     uint8_t *disk_dev = nullptr;
     std::vector<void *> allocs;
@@ -401,19 +372,21 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
         }
 
     const bool fp16 = (prob->flags & FPM_FLAG_SPEC_FP16) != 0;
-    c->fused_nt = fused_threads(np, r, L, st);
-    c->fused_mr = !c->fused_nt && fused_mr_supported(np, r, st);
     // Np 90 (configs 1 / 2): the register-transform kernel unless FPM_NO_S90=1
     // selects the generic small-patch kernel
-    c->fused_s90 = !c->fused_nt && !c->fused_mr && !getenv("FPM_NO_S90") && fused_s90_supported(np, r, st);
-    c->fused_small = !c->fused_nt && !c->fused_mr && !c->fused_s90 && fused_small_supported(np, r, st);
-    const bool fused_ok = c->fused_nt || c->fused_mr || c->fused_s90 || c->fused_small;
+    const Kernel fused = fused_threads(np, r, L, st)                                  ? Kernel::Np256
+                         : fused_mr_supported(np, r, st)                              ? Kernel::Np200
+                         : !getenv("FPM_NO_S90") && fused_s90_supported(np, r, st)    ? Kernel::Np90
+                         : fused_small_supported(np, r, st)                           ? Kernel::Small
+                                                                                      : Kernel::General;
+    const bool fused_ok = fused != Kernel::General;
     if (prob->path == FPM_PATH_FUSED && (fp16 || !fused_ok))
         return fail(set_err(FPM_ERR_INVAL, "fused path unsupported for Np=%d r=%d L=%d%s", np, r, L,
                             fp16 ? " with fp16 spectrum storage" : ""));
     c->path = (prob->path == FPM_PATH_GENERAL || fp16) ? FPM_PATH_GENERAL
               : fused_ok                               ? FPM_PATH_FUSED
                                                        : FPM_PATH_GENERAL;
+    if (c->path == FPM_PATH_FUSED) c->kernel = fused;
     // fp16 storage scale: 2^-ceil(log2 Np^2) (fpm_state.hpp)
     int e2 = 0;
     while ((1ll << e2) < (long long)np * np) ++e2;
@@ -478,18 +451,21 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
         if (c->ngroups > 1 && hipEventCreateWithFlags(&c->gfork, hipEventDisableTiming) != hipSuccess)
             return fail(set_err(FPM_ERR_DEVICE, "patch-group event creation failed"));
     } else {
-        c->meas_g = c->fused_small ? np : c->fused_s90 ? 9 : c->fused_mr ? 10 : 16;
+        c->meas_g = c->row().meas_g < 0 ? np : c->row().meas_g;
         if ((rc = dalloc(c, &st.T, fused_T_elems(np, r, B)))) return fail(rc);
         int n_cu = 0;
         (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device);
         // small batches: every phase distributed over KS workgroups per patch
         // (fused_dist.hip), else split mode (column parts only), else one
         // workgroup per patch
-        const int dks = c->fused_nt ? fused_dist_parts(B, n_cu, r, L) : 0;
-        c->dist = dks > 1;
-        c->split_ks = c->dist ? dks : c->fused_nt ? fused_split_parts(c->fused_nt, B, n_cu) : 1;
+        if (c->kernel == Kernel::Np256) {
+            const int dks = fused_dist_parts(B, n_cu, r, L);
+            if (dks > 1) c->kernel = Kernel::Np256Dist;
+            c->split_ks = dks > 1 ? dks : fused_split_parts(c->row().threads, B, n_cu);
+        }
         if (c->split_ks > 1) {
-            const size_t nx = c->dist ? fused_dist_elems(B, c->split_ks) : fused_xch_elems(B, c->split_ks);
+            const size_t nx = c->kernel == Kernel::Np256Dist ? fused_dist_elems(B, c->split_ks)
+                                                             : fused_xch_elems(B, c->split_ks);
             if ((rc = dalloc(c, &c->xch, nx))) return fail(rc);
             // distributed mode's tile words start at tag 0, which no LED uses
             if (hipMemset(c->xch, 0, nx * sizeof(float2)) != hipSuccess)
@@ -775,32 +751,27 @@ int fpm_run(fpm_ctx *c, int iters) {
         const int r = general_graph(c);
         if (r != FPM_OK) return r;
     }
+    const FusedLaunch in{c->meas, c->order_dev, c->x0_dev, c->y0_dev, c->prob.n_order, c->tw_np, c->dbg};
     hipEvent_t *ev = c->evpool.data();
     HIP_TRY(hipEventRecord(ev[0], c->stream));
     for (int it = 0; it < iters; ++it) {
         HIP_TRY(hipEventRecord(ev[1 + 3 * it], c->stream));
-        if (c->path == FPM_PATH_FUSED && c->fused_s90) {
-            HIP_TRY(launch_fused_s90_iteration(c->st, c->meas, c->order_dev, c->x0_dev, c->y0_dev,
-                                               c->prob.n_order, c->tw_np, c->dbg, c->stream));
-        } else if (c->path == FPM_PATH_FUSED && c->fused_small) {
-            HIP_TRY(launch_fused_small_iteration(c->st, c->meas, c->order_dev, c->x0_dev, c->y0_dev,
-                                                 c->prob.n_order, c->tw_np, c->pl_np, c->dbg, c->stream));
-        } else if (c->path == FPM_PATH_FUSED && c->fused_mr) {
-            HIP_TRY(launch_fused_mr_iteration(c->st, c->meas, c->order_dev, c->x0_dev, c->y0_dev,
-                                              c->prob.n_order, c->tw_np, c->dbg, c->stream));
-        } else if (c->path == FPM_PATH_FUSED && c->dist) {
-            HIP_TRY(launch_fused_dist(c->st, c->meas, c->order_dev, c->x0_dev, c->y0_dev, c->prob.n_order, c->tw_np,
-                                      c->split_ks, c->dbg, c->xch, c->split_flags, c->stall_led, c->dist_tags,
+        switch (c->kernel) {
+        case Kernel::Np90: HIP_TRY(launch_fused_s90_iteration(c->st, in, c->stream)); break;
+        case Kernel::Small: HIP_TRY(launch_fused_small_iteration(c->st, in, c->pl_np, c->stream)); break;
+        case Kernel::Np200: HIP_TRY(launch_fused_mr_iteration(c->st, in, c->stream)); break;
+        case Kernel::Np256Dist:
+            HIP_TRY(launch_fused_dist(c->st, in, c->split_ks, c->xch, c->split_flags, c->stall_led, c->dist_tags,
                                       c->stream));
             c->dist_tags = (c->dist_tags + (unsigned)c->prob.n_order) & 0x7fffffffu;
-        } else if (c->path == FPM_PATH_FUSED) {
-            HIP_TRY(launch_fused_iteration(c->st, c->meas, c->order_dev, c->x0_dev, c->y0_dev,
-                                           c->prob.n_order, c->tw_np, c->split_ks, c->dbg, c->xch,
-                                           c->split_flags, c->stall_led, c->stream));
-        } else if (use_graph) {
-            HIP_TRY(launch_general_graphs(c, c->stream));
-        } else {
-            HIP_TRY(launch_general_iteration(c, c->stream));
+            break;
+        case Kernel::Np256:
+            HIP_TRY(launch_fused_iteration(c->st, in, c->split_ks, c->xch, c->split_flags, c->stall_led, c->stream));
+            break;
+        case Kernel::General:
+            if (use_graph) HIP_TRY(launch_general_graphs(c, c->stream));
+            else HIP_TRY(launch_general_iteration(c, c->stream));
+            break;
         }
         HIP_TRY(hipEventRecord(ev[2 + 3 * it], c->stream));
         if (!last_only || it == iters - 1) {
@@ -846,12 +817,7 @@ int fpm_run(fpm_ctx *c, int iters) {
         HIP_TRY(hipMemcpy(h, c->dbg, sizeof h, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemset(c->dbg, 0, sizeof h));
         const double steps = (double)iters * c->prob.n_order * c->st.B;
-        const char *names_f[kStamps] = {"gather", "A:tail+sync", "B:columns", "C:tail+sync", "upd:sync+Opre", "max",
-                                        "P",      "A:rowIDFT",   "C:rowDFT",  "upd:body",    "B:loop",
-                                        "split:Fstores", "split:Fwait"};
-        const char *names_d[kStamps] = {"gather", "A", "sync1", "B", "sync2", "C", "update", "sync3",
-                                        "merge+Opre", "max", "P", "C:rows(sub)", "sync3:acks(sub)"};
-        const char *const *names = c->dist ? names_d : names_f;
+        const char *const *names = c->row().stamps;
         for (int v = 0; v < 2; ++v) {
             fprintf(stderr, "[fpm stamps] cycles per LED step (%s wave view, mean over blocks):", v ? "last" : "first");
             for (int i = 0; i < kStamps; ++i) fprintf(stderr, " %s=%.0f", names[i], h[v * kStamps + i] / steps);
@@ -971,16 +937,8 @@ static void fill_info(const fpm_ctx *c, fpm_info *info) {
     info->device = c->device;
     info->device_bytes = c->bytes;
     info->wg_per_patch = c->split_ks;
-    info->fused_kernel = c->path != FPM_PATH_FUSED ? FPM_KERNEL_GENERAL
-                         : c->fused_s90        ? FPM_KERNEL_FUSED_NP90
-                         : c->fused_small      ? FPM_KERNEL_FUSED_SMALL
-                         : c->fused_mr         ? FPM_KERNEL_FUSED_NP200
-                         : c->dist             ? FPM_KERNEL_FUSED_NP256_DIST
-                                               : FPM_KERNEL_FUSED_NP256;
-    info->threads_per_wg = c->path != FPM_PATH_FUSED ? 0
-                           : c->fused_s90 || c->fused_small ? 1024
-                           : c->fused_mr ? 768
-                                         : c->fused_nt;
+    info->fused_kernel = c->row().code;
+    info->threads_per_wg = c->row().threads;
 }
 
 int fpm_get_info_sized(const fpm_ctx *c, fpm_info *info, size_t info_size) {

@@ -42,7 +42,9 @@
 #include "fused256.hpp"
 #include "fused_common.hpp"
 #include "fused_sync.hpp"
+#include "launch.hpp"
 #include "ledtab.hpp"
+#include "tilemax.hpp"
 #include "update.hpp"
 
 namespace fpm {
@@ -94,8 +96,8 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
     int2 *tpx = (int2 *)(sig + 96);                 // MAXTAIL tail pixels (ky, kx)
     int *tky = (int *)(tpx + MAXTAIL);              // MAXTAILROWS tail rows
     float *tmx = (float *)(tky + MAXTAILROWS);      // nbt: max|spec| per band tile (upper bound if dirty)
-    unsigned *dirty = (unsigned *)(tmx + a.nbt);    // nbt bits: tile max may be stale-high
-    int *ccnt = (int *)(dirty + ((a.nbt + 31) >> 5));  // [0] pass-B column-block counter, [1] handoff result
+    unsigned *dirty = (unsigned *)(tmx + a.band.nbt);    // nbt bits: tile max may be stale-high
+    int *ccnt = (int *)(dirty + ((a.band.nbt + 31) >> 5));  // [0] pass-B column-block counter, [1] handoff result
 
     const DevState &st = a.st;
     const int tid = threadIdx.x, g = tid >> 4, t = tid & 15, gg = (tid >> 4) & 3;
@@ -115,7 +117,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
     int *xccs = split ? a.flags + KS * st.B + 1 + KS * b : nullptr;  // [KS]: XCC_ID + 1 of each part
     const int R = st.r, NB = st.nb, L = st.L;
     float2 *scr = scr_all + g * C::XT;
-    const int nwords = (a.nbt + 31) >> 5;
+    const int nwords = (a.band.nbt + 31) >> 5;
 
     // ---- one-time setup (kernel-argument tables indexed with uniform indices only)
     if (tid == 0) {
@@ -141,14 +143,14 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
     }
     // band tiles k <-> global tile (bty0 + k / nbx, btx0 + k % nbx); (k + 0.5) / nbx
     // is never within float rounding of an integer for k < 2^16
-    auto band_dy = [&](int k) { return (int)(((float)k + 0.5f) * a.rnbx); };
+    auto band_dy = [&](int k) { return (int)(((float)k + 0.5f) * a.band.rnbx); };
     auto band_gtile = [&](int k) {
         const int dy = band_dy(k);
-        return (a.bty0 + dy) * st.ntx + a.btx0 + (k - dy * a.nbx);
+        return (a.band.bty0 + dy) * st.ntx + a.band.btx0 + (k - dy * a.band.nbx);
     };
     float *tmax_g = st.tmax + (size_t)b * st.ntx * st.nty;
     unsigned *dirty_g = st.tdirty + (size_t)b * ((st.ntx * st.nty + 31) / 32);
-    for (int k = tid; k < a.nbt; k += NT) tmx[k] = tmax_g[band_gtile(k)];
+    for (int k = tid; k < a.band.nbt; k += NT) tmx[k] = tmax_g[band_gtile(k)];
     for (int i = tid; i < nwords; i += NT) dirty[i] = dirty_g[i];
 
     float2 *spec = st.spec + (size_t)b * L * L;
@@ -277,14 +279,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
     __syncthreads();
 
     // diagnostic: shader-clock cycles per phase, summed over LEDs (wave-uniform)
-    unsigned long long acc[kStamps] = {};  // phases: see api.cpp stamp names
-    unsigned long long prev = a.dbg ? __builtin_amdgcn_s_memtime() : 0ull;
-#define FPM_STAMP(i)                                                  \
-    if (a.dbg) {                                                      \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        acc[i] += now_ - prev;                                        \
-        prev = now_;                                                  \
-    }
+    FPM_STAMPS_BEGIN()
     // O (pre-update Objfcrop on the support, fpmMain.cpp:358-362) is never
     // held in registers through pass B: Opre is loaded at the start of pass C
     // for the second half's pass A and the object update, and right after the
@@ -590,7 +585,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
         // needed (64 lanes of a wave hit 2-4 tile words, and an unfiltered
         // LDS atomic serialises them: 3.7k cycles per LED).
         auto note = [&](int py, int px, float ao, float an) {
-            const int ti = ((py >> 4) - a.bty0) * a.nbx + ((px >> 4) - a.btx0);  // band tile
+            const int ti = ((py >> 4) - a.band.bty0) * a.band.nbx + ((px >> 4) - a.band.btx0);  // band tile
             const unsigned cur = tmu[ti];
             if (an < ao && cur <= __float_as_uint(ao)) atomicOr(&dirty[ti >> 5], 1u << (ti & 31));
             if (__float_as_uint(an) > cur) atomicMax(&tmu[ti], __float_as_uint(an));
@@ -641,8 +636,8 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
         // ---- exact max|objF| (:460,467): max over clean tiles; dirty tiles
         // only matter (and are re-read) when their bound exceeds that max
         float cm = 0.f, dm = 0.f;
-        for (int k = tid; k < a.nbt; k += NT) {
-            const bool d = (dirty[k >> 5] >> (k & 31)) & 1u;
+        for (int k = tid; k < a.band.nbt; k += NT) {
+            const bool d = tile_dirty(dirty, k);
             if (d) dm = fmaxf(dm, tmx[k]);
             else cm = fmaxf(cm, tmx[k]);
         }
@@ -662,9 +657,9 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
         }
         float omax = cm;
         if (dm > cm) {  // block-uniform: rare (bright-field LEDs, first LED of an iteration)
-            for (int k = w; k < a.nbt; k += NW) {
-                if (!((dirty[k >> 5] >> (k & 31)) & 1u) || !(tmx[k] > cm)) continue;  // wave-uniform
-                const int ty = a.bty0 + band_dy(k), tx = a.btx0 + k - band_dy(k) * a.nbx;
+            for (int k = w; k < a.band.nbt; k += NW) {
+                if (!tile_dirty(dirty, k) || !(tmx[k] > cm)) continue;  // wave-uniform
+                const int ty = a.band.bty0 + band_dy(k), tx = a.band.btx0 + k - band_dy(k) * a.band.nbx;
                 float2 e[4];  // all four loads before the first use (else one round trip each)
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
@@ -682,8 +677,8 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
             }
             __syncthreads();
             float m2 = 0.f;
-            for (int k = tid; k < a.nbt; k += NT)
-                if (!((dirty[k >> 5] >> (k & 31)) & 1u)) m2 = fmaxf(m2, tmx[k]);
+            for (int k = tid; k < a.band.nbt; k += NT)
+                if (!tile_dirty(dirty, k)) m2 = fmaxf(m2, tmx[k]);
             m2 = wave_max_nonneg(m2);
             __syncthreads();  // red[] reads above are done
             if (lane == 0) red[w] = m2;
@@ -721,7 +716,6 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
         FPM_STAMP(6)
         (void)aborted;
     }
-#undef FPM_STAMP
     __syncthreads();  // the last LED's red[32..]
     probe.stop(a.st.clk);
     if (pupil_done) pm = pm_of_red();
@@ -738,7 +732,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
         for (int s = 0; s < 6; ++s)
             if ((inmask[j] >> s) & 1) pup[(kyr[j] + R) * NB + slot_kx(t, s) + R] = P[j][s];
     if (towner) pup[(tp.x + R) * NB + tp.y + R] = Pt;
-    for (int k = tid; k < a.nbt; k += NT) tmax_g[band_gtile(k)] = tmx[k];
+    for (int k = tid; k < a.band.nbt; k += NT) tmax_g[band_gtile(k)] = tmx[k];
     for (int i = tid; i < nwords; i += NT) dirty_g[i] = dirty[i];
     if (tid == 0) st.pmax[b] = pm;
 }
@@ -759,9 +753,8 @@ size_t fused_lds_bytes(int ks, int nbt, int n_tail_rows) {
 int fused_threads(int np, int r, int L, const DevState &st) {
     const FusedGeom g = fused_geometry(np, r);
     if (!g.ok || L % kTile != 0) return 0;
-    if (st.sy0 < 0 || st.sy1 >= L || st.sy0 > st.sy1 || st.sx0 < 0 || st.sx1 >= L || st.sx0 > st.sx1) return 0;
-    const Band bd = band_of(st);
-    return fused_lds_bytes(1, bd.nbt, g.n_tail_rows) <= 160 * 1024 ? 512 : 0;
+    if (!band_valid(st)) return 0;
+    return fused_lds_bytes(1, band_of(st).nbt, g.n_tail_rows) <= kLdsCap ? 512 : 0;
 }
 
 size_t fused_T_elems(int, int, int) { return 1; }  // the intermediate lives in LDS
@@ -788,72 +781,24 @@ int fused_split_parts(int nt, int B, int n_cu) {
     return fits(4) ? 4 : fits(2) ? 2 : 1;
 }
 
-hipError_t launch_fused_iteration(const DevState &st, const uint16_t *meas, const int *order_dev,
-                                  const int *x0_dev, const int *y0_dev, int n_order, const float2 *tw_np,
-                                  int ks, unsigned long long *dbg, float2 *xch, int *flags, int stall_led,
-                                  hipStream_t s) {
+hipError_t launch_fused_iteration(const DevState &st, const FusedLaunch &in, int ks, float2 *xch, int *flags,
+                                  int stall_led, hipStream_t s) {
     const FusedGeom g = fused_geometry(st.np, st.r);
     if (!g.ok) return hipErrorInvalidValue;
     if (ks != 1 && ((ks != 2 && ks != 4) || !xch || !flags)) return hipErrorInvalidValue;
-    if (st.sy0 < 0 || st.sy1 >= st.L || st.sy0 > st.sy1 || st.sx0 < 0 || st.sx1 >= st.L || st.sx0 > st.sx1)
-        return hipErrorInvalidValue;
-    FusedArgs a;
-    a.st = st;
-    a.meas = meas;
-    a.order = order_dev;
-    a.x0 = x0_dev;
-    a.y0 = y0_dev;
-    a.tw = tw_np;
-    a.n_order = n_order;
-    a.ky_lo = g.ky_lo;
-    a.n_fft_rows = g.n_fft_rows;
-    a.n_tail_rows = g.n_tail_rows;
-    for (int i = 0; i < fz::MAXTAILROWS; ++i) a.tail_ky[i] = g.tail_ky[i];
-    a.n_tail_px = g.n_tail_px;
-    for (int q = 0; q < fz::MAXTAILROWS; ++q) {
-        a.tail_row_p0[q] = a.tail_row_np[q] = a.tail_row_kx0[q] = 0;
-        for (int p = 0; p < g.n_tail_px && q < g.n_tail_rows; ++p)
-            if (g.tail_px[p].x == g.tail_ky[q]) {
-                if (a.tail_row_np[q] == 0) {
-                    a.tail_row_p0[q] = p;
-                    a.tail_row_kx0[q] = g.tail_px[p].y;
-                }
-                ++a.tail_row_np[q];
-            }
-    }
-    for (int i = 0; i < fz::MAXTAIL; ++i) a.tail_px[i] = i < g.n_tail_px ? g.tail_px[i] : make_int2(0, 0);
-    const Band bd = band_of(st);
-    a.bty0 = bd.bty0;
-    a.btx0 = bd.btx0;
-    a.nbx = bd.nbx;
-    a.nbt = bd.nbt;
-    a.rnbx = 1.0f / (float)a.nbx;
-    a.dbg = dbg;
+    if (!band_valid(st)) return hipErrorInvalidValue;
+    FusedArgs a{};
+    fill_np256_args(a, st, g, in);
     a.xch = ks > 1 ? xch : nullptr;
     a.flags = ks > 1 ? flags : nullptr;
     a.abort_flag = ks > 1 ? flags + ks * st.B : nullptr;
     a.stall_led = ks > 1 ? stall_led : -1;
-    const size_t lds0 = fused_lds_bytes(ks, a.nbt, g.n_tail_rows);
-    if (lds0 > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds0 = fused_lds_bytes(ks, a.band.nbt, g.n_tail_rows);
+    if (lds0 > kLdsCap) return hipErrorInvalidValue;
     size_t lds;  // + the LED table when it fits
-    a.ledtab_off = ledtab_offset(lds0, n_order, st.L, 160 * 1024, lds);
-    const void *fn = ks == 4   ? (const void *)k_fused_iteration<512, 4>
-                     : ks == 2 ? (const void *)k_fused_iteration<512, 2>
-                               : (const void *)k_fused_iteration<512, 1>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (ks > 1) {
-        // flags count LEDs of this launch and XCC ids are re-learnt: both start
-        // from zero; the abort word between them is sticky (fpm_run reads and
-        // clears it, so a timeout in any iteration of a multi-iteration run
-        // is reported, and every later launch leaves at once)
-        e = hipMemsetAsync(flags, 0, (size_t)ks * st.B * sizeof(int), s);
-        if (e == hipSuccess) e = hipMemsetAsync(flags + ks * st.B + 1, 0, (size_t)ks * st.B * sizeof(int), s);
-        if (e != hipSuccess) return e;
-        return launch_coresident(fn, 8 * ks * ((st.B + 7) / 8), 512, lds, &a, s);
-    }
-    hipLaunchKernelGGL((k_fused_iteration<512, 1>), dim3(st.B), dim3(512), lds, s, a);
-    return hipGetLastError();
+    a.ledtab_off = ledtab_offset(lds0, in.n_order, st.L, kLdsCap, lds);
+    if (ks == 1) return launch_lds(k_fused_iteration<512, 1>, st.B, 512, lds, &a, s);
+    return launch_np256_parts(ks == 4 ? k_fused_iteration<512, 4> : k_fused_iteration<512, 2>, ks, lds, &a, s);
 }
 
 }  // namespace fpm

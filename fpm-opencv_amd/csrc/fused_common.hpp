@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fpm_state.hpp"
+#include "fused_host.hpp"
 #include "fused_sync.hpp"
 
 namespace fpm {
@@ -31,12 +32,7 @@ struct FusedArgs {
     int2 tail_px[fz::MAXTAIL];  // (ky, kx), sorted by row then kx
     // tail row q holds pixels tail_px[p0 .. p0+np) with kx = kx0, kx0+1, ...
     int tail_row_p0[fz::MAXTAILROWS], tail_row_np[fz::MAXTAILROWS], tail_row_kx0[fz::MAXTAILROWS];
-    // tiles of the spectrum's live band (fpm_state.hpp): every other tile is
-    // exactly 0 and never changes, so the kernel keeps maxima and dirty bits
-    // for these nbt tiles only (band tile k = (bty0 + k / nbx, btx0 + k % nbx));
-    // st.tdirty holds the band-indexed bits between launches
-    int btx0, bty0, nbx, nbt;
-    float rnbx;                 // 1 / nbx
+    BandArgs band;              // tiles of the spectrum's live band (tilemax.hpp)
     unsigned long long *dbg;    // diagnostic phase stamps (FPM_STAMPS=1), else null
     // split mode (NT 512, KS = 2 or 4 workgroups per patch, KS * B <= CUs):
     // workgroup p owns column part p (256 / KS columns); handoffs through xch
@@ -102,16 +98,53 @@ inline FusedGeom fused_geometry(int np, int r) {
     return g;
 }
 
-struct Band {
-    int bty0, btx0, nbx, nbt;
-};
-inline Band band_of(const DevState &st) {
-    Band b;
-    b.bty0 = st.sy0 / kTile;
-    b.btx0 = st.sx0 / kTile;
-    b.nbx = st.sx1 / kTile - b.btx0 + 1;
-    b.nbt = b.nbx * (st.sy1 / kTile - b.bty0 + 1);
-    return b;
+// The arguments both Np 256 kernels share: the launch inputs, the row split
+// of the support box (fused_geometry) with the tail-row tables, the band
+// tiles.  The mode's own fields (xch, flags, abort_flag, stall_led, tag_base,
+// ledtab_off) stay with the launcher.
+inline void fill_np256_args(FusedArgs &a, const DevState &st, const FusedGeom &g, const FusedLaunch &in) {
+    a.st = st;
+    a.meas = in.meas;
+    a.order = in.order;
+    a.x0 = in.x0;
+    a.y0 = in.y0;
+    a.tw = in.tw;
+    a.n_order = in.n_order;
+    a.ky_lo = g.ky_lo;
+    a.n_fft_rows = g.n_fft_rows;
+    a.n_tail_rows = g.n_tail_rows;
+    for (int i = 0; i < fz::MAXTAILROWS; ++i) a.tail_ky[i] = g.tail_ky[i];
+    a.n_tail_px = g.n_tail_px;
+    for (int q = 0; q < fz::MAXTAILROWS; ++q) {
+        a.tail_row_p0[q] = a.tail_row_np[q] = a.tail_row_kx0[q] = 0;
+        for (int p = 0; p < g.n_tail_px && q < g.n_tail_rows; ++p)
+            if (g.tail_px[p].x == g.tail_ky[q]) {
+                if (a.tail_row_np[q] == 0) {
+                    a.tail_row_p0[q] = p;
+                    a.tail_row_kx0[q] = g.tail_px[p].y;
+                }
+                ++a.tail_row_np[q];
+            }
+    }
+    for (int i = 0; i < fz::MAXTAIL; ++i) a.tail_px[i] = i < g.n_tail_px ? g.tail_px[i] : make_int2(0, 0);
+    a.band = band_of(st);
+    a.dbg = in.dbg;
+}
+
+// Launch of a grid with KS workgroups per patch that wait on each other (split
+// and distributed modes; a.flags set): flags count the handoffs of this
+// launch and XCC ids are re-learnt, so both start from zero; the abort word
+// between them is sticky (fpm_run reads and clears it, so a timeout in any
+// iteration of a multi-iteration run is reported, and every later launch
+// leaves at once).  Grid rounded up to 8 KS blocks (the kernels' block map).
+inline hipError_t launch_np256_parts(void (*fn)(FusedArgs), int ks, size_t lds, FusedArgs *a, hipStream_t s) {
+    const int B = a->st.B;
+    hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(a->flags, 0, (size_t)ks * B * sizeof(int), s);
+    if (e == hipSuccess) e = hipMemsetAsync(a->flags + ks * B + 1, 0, (size_t)ks * B * sizeof(int), s);
+    if (e != hipSuccess) return e;
+    return launch_coresident((const void *)fn, 8 * ks * ((B + 7) / 8), 512, lds, a, s);
 }
 
 }  // namespace fpm

@@ -45,7 +45,9 @@
 #include "fused256.hpp"
 #include "fused_common.hpp"
 #include "fused_sync.hpp"
+#include "launch.hpp"
 #include "ledtab.hpp"
+#include "tilemax.hpp"
 #include "update.hpp"
 
 namespace fpm {
@@ -82,8 +84,8 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
     int2 *tpx = (int2 *)(sig + 96);                 // MAXTAIL tail pixels (ky, kx)
     int *tpq = (int *)(tpx + MAXTAIL);              // MAXTAIL: tail row of each tail pixel
     float *tmx = (float *)(tpq + MAXTAIL);          // nbt: max|spec| per band tile (upper bound if dirty)
-    unsigned *dirty = (unsigned *)(tmx + a.nbt);    // nbt bits
-    int *ccnt = (int *)(dirty + ((a.nbt + 31) >> 5));  // [0] pass-B block counter, [1] handoff result
+    unsigned *dirty = (unsigned *)(tmx + a.band.nbt);    // nbt bits
+    int *ccnt = (int *)(dirty + ((a.band.nbt + 31) >> 5));  // [0] pass-B block counter, [1] handoff result
 
     const DevState &st = a.st;
     const int tid = threadIdx.x, g = tid >> 4, t = tid & 15, gg = (tid >> 4) & 3;
@@ -99,7 +101,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
     int *xccs = a.flags + KS * st.B + 1 + KS * b;
     const int R = st.r, NB = st.nb, L = st.L;
     float2 *scr = scr_all + g * XTILE;
-    const int nwords = (a.nbt + 31) >> 5;
+    const int nwords = (a.band.nbt + 31) >> 5;
     // spread object update (KS 8): F, O, P of the own rows' slots staged in
     // the exchange tiles of the groups that own no FFT row (free in C and the
     // update).  32-patch shard 2.74 -> 2.83 M (update 3.6k -> 2.2k cycles per
@@ -139,14 +141,14 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
         }
         sig[i] = s;
     }
-    auto band_dy = [&](int k) { return (int)(((float)k + 0.5f) * a.rnbx); };
+    auto band_dy = [&](int k) { return (int)(((float)k + 0.5f) * a.band.rnbx); };
     auto band_gtile = [&](int k) {
         const int dy = band_dy(k);
-        return (a.bty0 + dy) * st.ntx + a.btx0 + (k - dy * a.nbx);
+        return (a.band.bty0 + dy) * st.ntx + a.band.btx0 + (k - dy * a.band.nbx);
     };
     float *tmax_g = st.tmax + (size_t)b * st.ntx * st.nty;
     unsigned *dirty_g = st.tdirty + (size_t)b * ((st.ntx * st.nty + 31) / 32);
-    for (int k = tid; k < a.nbt; k += NT) tmx[k] = tmax_g[band_gtile(k)];
+    for (int k = tid; k < a.band.nbt; k += NT) tmx[k] = tmax_g[band_gtile(k)];
     for (int i = tid; i < nwords; i += NT) dirty[i] = dirty_g[i];
 
     float2 *spec = st.spec + (size_t)b * L * L;
@@ -251,14 +253,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
     constexpr int WMERGE = KS == 8 ? NW - 1 : 0;
     unsigned *omx = (unsigned *)(red + 40);  // [0] clean / [1] dirty max over the tiles outside the window
 
-    unsigned long long acc[kStamps] = {};
-    unsigned long long prev = a.dbg ? __builtin_amdgcn_s_memtime() : 0ull;
-#define FPM_STAMP(i)                                                  \
-    if (a.dbg) {                                                      \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        acc[i] += now_ - prev;                                        \
-        prev = now_;                                                  \
-    }
+    FPM_STAMPS_BEGIN()
     auto soff = [](int s) { return 16 * fz::SK[s] - (s >= 3 ? fz::NP : 0); };
     // window of LED `itn` in the centred spectrum: element offset of (ky, kx) = (0, 0)
     auto wbase = [&](int itn) {
@@ -340,11 +335,11 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
         const int wty1 = (yc + R) >> 4, wtx1 = (xc + R) >> 4;
         if (!handoff([&]() {
                 float c = 0.f, d = 0.f;
-                for (int k = tid - 64; k < a.nbt; k += NT - 64) {
-                    const int dy = band_dy(k), ty = a.bty0 + dy, tx = a.btx0 + k - dy * a.nbx;
+                for (int k = tid - 64; k < a.band.nbt; k += NT - 64) {
+                    const int dy = band_dy(k), ty = a.band.bty0 + dy, tx = a.band.btx0 + k - dy * a.band.nbx;
                     if (ty >= wty0 && ty <= wty1 && tx >= wtx0 && tx <= wtx1) continue;
                     const float v = tmx[k];
-                    if ((dirty[k >> 5] >> (k & 31)) & 1u) d = fmaxf(d, v);
+                    if (tile_dirty(dirty, k)) d = fmaxf(d, v);
                     else c = fmaxf(c, v);
                 }
                 c = wave_max_nonneg(c);
@@ -510,7 +505,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
 
         // ---- object update of the own rows (:405-447), pupil numerator (:457-464)
         auto note = [&](int py, int px, float ao, float an) {
-            const int ti = ((py >> 4) - a.bty0) * a.nbx + ((px >> 4) - a.btx0);
+            const int ti = ((py >> 4) - a.band.bty0) * a.band.nbx + ((px >> 4) - a.band.btx0);
             const unsigned cur = tmu[ti];
             if (an < ao && cur <= __float_as_uint(ao)) atomicOr(&dirty[ti >> 5], 1u << (ti & 31));
             if (__float_as_uint(an) > cur) atomicMax(&tmu[ti], __float_as_uint(an));
@@ -567,7 +562,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
         const int wnx = wtx1 - wtx0 + 1, wnt = wnx * (wty1 - wty0 + 1);
         auto wtile = [&](int k) {  // band index of window tile k
             const int dy = k / wnx;
-            return (wty0 + dy - a.bty0) * a.nbx + (wtx0 + k - dy * wnx - a.btx0);
+            return (wty0 + dy - a.band.bty0) * a.band.nbx + (wtx0 + k - dy * wnx - a.band.btx0);
         };
         if (w == WMERGE) {
             // thread ti < wnt owns window tile ti (see towner: ti spans 0..63
@@ -647,9 +642,9 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
         const float cm = red[0], dm = red[16];
         float omax = cm;
         if (dm > cm) {
-            for (int k = w; k < a.nbt; k += NW) {
-                if (!((dirty[k >> 5] >> (k & 31)) & 1u) || !(tmx[k] > cm)) continue;
-                const int ty = a.bty0 + band_dy(k), tx = a.btx0 + k - band_dy(k) * a.nbx;
+            for (int k = w; k < a.band.nbt; k += NW) {
+                if (!tile_dirty(dirty, k) || !(tmx[k] > cm)) continue;
+                const int ty = a.band.bty0 + band_dy(k), tx = a.band.btx0 + k - band_dy(k) * a.band.nbx;
                 float2 e[4];  // all four loads before the first use
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
@@ -667,8 +662,8 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
             }
             __syncthreads();
             float m2 = 0.f;
-            for (int k = tid; k < a.nbt; k += NT)
-                if (!((dirty[k >> 5] >> (k & 31)) & 1u)) m2 = fmaxf(m2, tmx[k]);
+            for (int k = tid; k < a.band.nbt; k += NT)
+                if (!tile_dirty(dirty, k)) m2 = fmaxf(m2, tmx[k]);
             m2 = wave_max_nonneg(m2);
             __syncthreads();
             if (lane == 0) red[w] = m2;
@@ -697,7 +692,6 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
         if (lane == 0) red[32 + w] = pmx;
         FPM_STAMP(10)
     }
-#undef FPM_STAMP
     __syncthreads();  // red[32..]
     probe.stop(a.st.clk);
 #ifndef FPM_STAMP_PART2
@@ -728,7 +722,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
         }
     }
     if (hown == 0) {
-        for (int k = tid; k < a.nbt; k += NT) tmax_g[band_gtile(k)] = tmx[k];
+        for (int k = tid; k < a.band.nbt; k += NT) tmax_g[band_gtile(k)] = tmx[k];
         for (int i = tid; i < nwords; i += NT) dirty_g[i] = dirty[i];
     }
     (void)pmx_part;
@@ -766,64 +760,23 @@ int fused_dist_parts(int B, int n_cu, int r, int L) {
     return fits(8) ? 8 : fits(4) ? 4 : 0;
 }
 
-hipError_t launch_fused_dist(const DevState &st, const uint16_t *meas, const int *order_dev, const int *x0_dev,
-                             const int *y0_dev, int n_order, const float2 *tw_np, int ks, unsigned long long *dbg,
-                             float2 *area, int *flags, int stall_led, unsigned tag_base, hipStream_t s) {
+hipError_t launch_fused_dist(const DevState &st, const FusedLaunch &in, int ks, float2 *area, int *flags,
+                             int stall_led, unsigned tag_base, hipStream_t s) {
     const FusedGeom g = fused_geometry(st.np, st.r);
     if (!g.ok || (ks != 2 && ks != 4 && ks != 8) || !area || !flags) return hipErrorInvalidValue;
-    if (st.sy0 < 0 || st.sy1 >= st.L || st.sy0 > st.sy1 || st.sx0 < 0 || st.sx1 >= st.L || st.sx0 > st.sx1)
-        return hipErrorInvalidValue;
+    if (!band_valid(st)) return hipErrorInvalidValue;
     FusedArgs a{};
-    a.st = st;
-    a.meas = meas;
-    a.order = order_dev;
-    a.x0 = x0_dev;
-    a.y0 = y0_dev;
-    a.tw = tw_np;
-    a.n_order = n_order;
-    a.ky_lo = g.ky_lo;
-    a.n_fft_rows = g.n_fft_rows;
-    a.n_tail_rows = g.n_tail_rows;
-    for (int i = 0; i < fz::MAXTAILROWS; ++i) a.tail_ky[i] = g.tail_ky[i];
-    a.n_tail_px = g.n_tail_px;
-    for (int q = 0; q < fz::MAXTAILROWS; ++q) {
-        a.tail_row_p0[q] = a.tail_row_np[q] = a.tail_row_kx0[q] = 0;
-        for (int p = 0; p < g.n_tail_px && q < g.n_tail_rows; ++p)
-            if (g.tail_px[p].x == g.tail_ky[q]) {
-                if (a.tail_row_np[q] == 0) {
-                    a.tail_row_p0[q] = p;
-                    a.tail_row_kx0[q] = g.tail_px[p].y;
-                }
-                ++a.tail_row_np[q];
-            }
-    }
-    for (int i = 0; i < fz::MAXTAIL; ++i) a.tail_px[i] = i < g.n_tail_px ? g.tail_px[i] : make_int2(0, 0);
-    const Band bd = band_of(st);
-    a.bty0 = bd.bty0;
-    a.btx0 = bd.btx0;
-    a.nbx = bd.nbx;
-    a.nbt = bd.nbt;
-    a.rnbx = 1.0f / (float)a.nbx;
-    a.dbg = dbg;
+    fill_np256_args(a, st, g, in);
     a.xch = area;
     a.flags = flags;
     a.abort_flag = flags + ks * st.B;
     a.stall_led = stall_led;
     a.tag_base = tag_base;
-    const size_t lds0 = fused_dist_lds_bytes(ks, a.nbt, g.n_tail_rows);
-    if (lds0 > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds0 = fused_dist_lds_bytes(ks, a.band.nbt, g.n_tail_rows);
+    if (lds0 > kLdsCap) return hipErrorInvalidValue;
     size_t lds;  // + the LED table when it fits
-    a.ledtab_off = ledtab_offset(lds0, n_order, st.L, 160 * 1024, lds);
-    const void *fn = ks == 8   ? (const void *)k_fused_dist<8>
-                     : ks == 4 ? (const void *)k_fused_dist<4>
-                               : (const void *)k_fused_dist<2>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    // handoff counters and XCC ids restart at zero; the abort word is sticky
-    e = hipMemsetAsync(flags, 0, (size_t)ks * st.B * sizeof(int), s);
-    if (e == hipSuccess) e = hipMemsetAsync(flags + ks * st.B + 1, 0, (size_t)ks * st.B * sizeof(int), s);
-    if (e != hipSuccess) return e;
-    return launch_coresident(fn, 8 * ks * ((st.B + 7) / 8), 512, lds, &a, s);
+    a.ledtab_off = ledtab_offset(lds0, in.n_order, st.L, kLdsCap, lds);
+    return launch_np256_parts(ks == 8 ? k_fused_dist<8> : ks == 4 ? k_fused_dist<4> : k_fused_dist<2>, ks, lds, &a, s);
 }
 
 }  // namespace fpm

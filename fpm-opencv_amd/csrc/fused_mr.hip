@@ -39,7 +39,9 @@
 #include "dft200.hpp"
 #include "fft_lds.hpp"
 #include "fpm_state.hpp"
+#include "fused_host.hpp"
 #include "fused_sync.hpp"
+#include "launch.hpp"
 #include "ledtab.hpp"
 #include "tilemax.hpp"
 #include "update.hpp"
@@ -87,8 +89,7 @@ struct FusedMRArgs {
     const int *order, *x0, *y0;
     const float2 *tw;        // exp(-2 pi i k / 200), k < 200
     int n_order;
-    int btx0, bty0, nbx, nbt;  // live-band tiles (fpm_fused.hip FusedArgs)
-    float rnbx;
+    BandArgs band;             // live-band tiles (tilemax.hpp)
     unsigned long long *dbg;   // FPM_STAMPS=1 phase cycles, else null
     int xw;                    // exchange tiles: wave slot (complex)
     int xg[fm::GPW];           // tile offset of group gw in the wave slot
@@ -115,8 +116,8 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
     unsigned *omx = (unsigned *)(red + 44);
     int *sig = (int *)(red + 48);              // 64: T row of ky in [-32, 31], -1 outside the box
     float *tmx = (float *)(sig + 64);          // nbt band-tile maxima
-    unsigned *dirty = (unsigned *)(tmx + a.nbt);
-    int *ccnt = (int *)(dirty + ((a.nbt + 31) >> 5));  // pass-B column-block counter
+    unsigned *dirty = (unsigned *)(tmx + a.band.nbt);
+    int *ccnt = (int *)(dirty + ((a.band.nbt + 31) >> 5));  // pass-B column-block counter
 
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int gw = lane / N2;                  // group within the wave (6 = idle lanes)
@@ -129,21 +130,21 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
     for (int i = 1; i < GPW; ++i) xgo = gw == i ? a.xg[i] : xgo;
     float2 *tile = tiles + w * a.xw + xgo;
     const int xrd = opaque_i(l * XP);
-    const int nwords = (a.nbt + 31) >> 5;
+    const int nwords = (a.band.nbt + 31) >> 5;
 
     for (int i = tid; i < 200; i += NT) tw2[i] = a.tw[((i / 10) * (i % 10)) % NP];
     for (int i = tid; i < 64; i += NT) {
         const int ky = i - KYOFF;
         sig[i] = (ky >= -R && ky <= R) ? ky + R : -1;
     }
-    auto band_dy = [&](int k) { return (int)(((float)k + 0.5f) * a.rnbx); };
+    auto band_dy = [&](int k) { return (int)(((float)k + 0.5f) * a.band.rnbx); };
     auto band_gtile = [&](int k) {
         const int dy = band_dy(k);
-        return (a.bty0 + dy) * st.ntx + a.btx0 + (k - dy * a.nbx);
+        return (a.band.bty0 + dy) * st.ntx + a.band.btx0 + (k - dy * a.band.nbx);
     };
     float *tmax_g = st.tmax + (size_t)b * st.ntx * st.nty;
     unsigned *dirty_g = st.tdirty + (size_t)b * ((st.ntx * st.nty + 31) / 32);
-    for (int k = tid; k < a.nbt; k += NT) tmx[k] = tmax_g[band_gtile(k)];
+    for (int k = tid; k < a.band.nbt; k += NT) tmx[k] = tmax_g[band_gtile(k)];
     for (int i = tid; i < nwords; i += NT) dirty[i] = dirty_g[i];
     const int zoff = NB * TLD;
     for (int i = tid; i < 2 * TLD; i += NT) th[zoff + i] = make_float2(0.f, 0.f);
@@ -181,14 +182,7 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
     const float epsn = st.eps * (float)(NP * NP);
     const float epsn_im = st.eps_im * (float)(NP * NP);
 
-    unsigned long long acc[kStamps] = {};
-    unsigned long long prev = a.dbg ? __builtin_amdgcn_s_memtime() : 0ull;
-#define FPM_STAMP(i)                                                  \
-    if (a.dbg) {                                                      \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        acc[i] += now_ - prev;                                        \
-        prev = now_;                                                  \
-    }
+    FPM_STAMPS_BEGIN()
     auto window = [&](int itn) {
         const LedPos p = lt.at(itn);
         return spec + (unsigned)(p.yc * L + p.xc);
@@ -300,7 +294,7 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
         // (:457-464); tile maxima kept exact incrementally (fpm_fused.hip)
         unsigned *tmu = (unsigned *)tmx;
         auto note = [&](int py, int px, float ao, float an) {
-            const int ti = ((py >> 4) - a.bty0) * a.nbx + ((px >> 4) - a.btx0);
+            const int ti = ((py >> 4) - a.band.bty0) * a.band.nbx + ((px >> 4) - a.band.btx0);
             const unsigned cur = tmu[ti];
             if (an < ao && cur <= __float_as_uint(ao)) atomicOr(&dirty[ti >> 5], 1u << (ti & 31));
             if (__float_as_uint(an) > cur) atomicMax(&tmu[ti], __float_as_uint(an));
@@ -322,8 +316,8 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
         // band tiles outside this LED's window, which no update touches
         if (w >= wi0) {
             float c, d;
-            const TileWin wn = tile_window(yc, xc, R, a.bty0, a.btx0);  // the band tiles this LED's update touches
-            outside_max(tmx, dirty, a.nbt, a.nbx, a.rnbx, wn, tid - 64 * wi0, NT - 64 * wi0, c, d);
+            const TileWin wn = tile_window(yc, xc, R, a.band.bty0, a.band.btx0);  // the band tiles this LED's update touches
+            outside_max(tmx, dirty, a.band.nbt, a.band.nbx, a.band.rnbx, wn, tid - 64 * wi0, NT - 64 * wi0, c, d);
             if (lane == 0) {  // >= 0: the float bits order as unsigned
                 atomicMax(&omx[0], __float_as_uint(c));
                 atomicMax(&omx[1], __float_as_uint(d));
@@ -343,8 +337,8 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
         // (tilemax.hpp) and hands them over through one barrier
         if (w == NW - 1) {
             float c, d;
-            const TileWin wn = tile_window(yc, xc, R, a.bty0, a.btx0);  // (recomputed: registers are short)
-            window_max(tmx, dirty, a.nbx, wn, lane, __uint_as_float(omx[0]), __uint_as_float(omx[1]), c, d);
+            const TileWin wn = tile_window(yc, xc, R, a.band.bty0, a.band.btx0);  // (recomputed: registers are short)
+            window_max(tmx, dirty, a.band.nbx, wn, lane, __uint_as_float(omx[0]), __uint_as_float(omx[1]), c, d);
             if (lane == 0) {
                 red[0] = c;
                 red[16] = d;
@@ -361,9 +355,9 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
         const float cm = red[0], dm = red[16];
         float omax = cm;
         if (dm > cm) {  // block-uniform
-            for (int k = w; k < a.nbt; k += NW) {
-                if (!((dirty[k >> 5] >> (k & 31)) & 1u) || !(tmx[k] > cm)) continue;  // wave-uniform
-                const int ty = a.bty0 + band_dy(k), tx = a.btx0 + k - band_dy(k) * a.nbx;
+            for (int k = w; k < a.band.nbt; k += NW) {
+                if (!tile_dirty(dirty, k) || !(tmx[k] > cm)) continue;  // wave-uniform
+                const int ty = a.band.bty0 + band_dy(k), tx = a.band.btx0 + k - band_dy(k) * a.band.nbx;
                 float mm = 0.f;
                 // the tile's four loads issued together (clamped in bounds, masked
                 // after): a conditional load waited for each in turn
@@ -387,8 +381,8 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
             }
             __syncthreads();
             float m2 = 0.f;
-            for (int k = tid; k < a.nbt; k += NT)
-                if (!((dirty[k >> 5] >> (k & 31)) & 1u)) m2 = fmaxf(m2, tmx[k]);
+            for (int k = tid; k < a.band.nbt; k += NT)
+                if (!tile_dirty(dirty, k)) m2 = fmaxf(m2, tmx[k]);
             m2 = wave_max_nonneg(m2);
             __syncthreads();
             if (lane == 0) red[w] = m2;
@@ -415,7 +409,6 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
         if (lane == 0) red[32 + w] = pmx;
         FPM_STAMP(6)
     }
-#undef FPM_STAMP
     auto fold_pm = [&]() {
         float pm2 = red[32];
 #pragma unroll
@@ -434,7 +427,7 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
 #pragma unroll
     for (int s = 0; s < 6; ++s)
         if ((inmask >> s) & 1) pup[(kyr + R) * NB + mr_kx(l, s) + R] = P[s];
-    for (int k = tid; k < a.nbt; k += NT) tmax_g[band_gtile(k)] = tmx[k];
+    for (int k = tid; k < a.band.nbt; k += NT) tmax_g[band_gtile(k)] = tmx[k];
     for (int i = tid; i < nwords; i += NT) dirty_g[i] = dirty[i];
     if (tid == 0) st.pmax[b] = pm;
 }
@@ -451,45 +444,32 @@ size_t mr_lds_bytes(int nb, int nbt, int xw = fm::XW_DENSE, int tld = fm::TLD) {
 // Np 200 fused kernel available for this geometry (r <= 29, T + tiles fit)?
 bool fused_mr_supported(int np, int r, const DevState &st) {
     if (np != fm::NP || r < 1 || r > fm::RMAX) return false;
-    if (st.sy0 < 0 || st.sy1 >= st.L || st.sy0 > st.sy1 || st.sx0 < 0 || st.sx1 >= st.L || st.sx0 > st.sx1)
-        return false;
-    const int bty0 = st.sy0 / kTile, btx0 = st.sx0 / kTile;
-    const int nbx = st.sx1 / kTile - btx0 + 1, nbt = nbx * (st.sy1 / kTile - bty0 + 1);
-    return mr_lds_bytes(2 * r + 1, nbt) <= 160 * 1024;
+    return band_valid(st) && mr_lds_bytes(2 * r + 1, band_of(st).nbt) <= kLdsCap;
 }
 
-hipError_t launch_fused_mr_iteration(const DevState &st, const uint16_t *meas, const int *order_dev,
-                                     const int *x0_dev, const int *y0_dev, int n_order, const float2 *tw_np,
-                                     unsigned long long *dbg, hipStream_t s) {
+hipError_t launch_fused_mr_iteration(const DevState &st, const FusedLaunch &in, hipStream_t s) {
     if (!fused_mr_supported(st.np, st.r, st)) return hipErrorInvalidValue;
     FusedMRArgs a;
     a.st = st;
-    a.meas = meas;
-    a.order = order_dev;
-    a.x0 = x0_dev;
-    a.y0 = y0_dev;
-    a.tw = tw_np;
-    a.n_order = n_order;
-    a.bty0 = st.sy0 / kTile;
-    a.btx0 = st.sx0 / kTile;
-    a.nbx = st.sx1 / kTile - a.btx0 + 1;
-    a.nbt = a.nbx * (st.sy1 / kTile - a.bty0 + 1);
-    a.rnbx = 1.0f / (float)a.nbx;
-    a.dbg = dbg;
+    a.meas = in.meas;
+    a.order = in.order;
+    a.x0 = in.x0;
+    a.y0 = in.y0;
+    a.tw = in.tw;
+    a.n_order = in.n_order;
+    a.band = band_of(st);
+    a.dbg = in.dbg;
     // bank-friendly strides while LDS allows: tiles first, then the T pitch
     // (FPM_MR_DENSE=1 forces the dense layout, test_gpu_fused_mr.py)
     const bool dense = getenv("FPM_MR_DENSE") != nullptr;
-    auto fits = [&](int xw, int tld) { return !dense && mr_lds_bytes(st.nb, a.nbt, xw, tld) <= 160 * 1024; };
+    auto fits = [&](int xw, int tld) { return !dense && mr_lds_bytes(st.nb, a.band.nbt, xw, tld) <= kLdsCap; };
     a.tld = fits(fm::XW_STRIDE, fm::TLD_FAST) ? fm::TLD_FAST : fm::TLD;
     a.xw = fits(fm::XW_SHIFT, a.tld) ? fm::XW_SHIFT : fits(fm::XW_STRIDE, a.tld) ? fm::XW_STRIDE : fm::XW_DENSE;
     for (int i = 0; i < fm::GPW; ++i)
         a.xg[i] = a.xw == fm::XW_SHIFT ? fm::XG_SHIFT[i] : i * (a.xw == fm::XW_STRIDE ? 106 : fm::XT);
     size_t lds;  // the kernel's own LDS + the LED table when it fits
-    a.ledtab_off = ledtab_offset(mr_lds_bytes(st.nb, a.nbt, a.xw, a.tld), n_order, st.L, 160 * 1024, lds);
-    hipError_t e = hipFuncSetAttribute((const void *)k_fused_mr, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fused_mr, dim3(st.B), dim3(fm::NT), lds, s, a);
-    return hipGetLastError();
+    a.ledtab_off = ledtab_offset(mr_lds_bytes(st.nb, a.band.nbt, a.xw, a.tld), in.n_order, st.L, kLdsCap, lds);
+    return launch_lds(k_fused_mr, st.B, fm::NT, lds, &a, s);
 }
 
 }  // namespace fpm

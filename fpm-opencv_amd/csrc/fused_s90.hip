@@ -31,7 +31,9 @@
 #include "dft90.hpp"
 #include "fft_lds.hpp"
 #include "fpm_state.hpp"
+#include "fused_host.hpp"
 #include "fused_sync.hpp"
+#include "launch.hpp"
 #include "ledtab.hpp"
 #include "tilemax.hpp"
 #include "update.hpp"
@@ -181,14 +183,7 @@ __global__ void __launch_bounds__(f90::NT, 1) k_fused_s90(FusedS90Args a) {
         if (__float_as_uint(an) > cur) atomicMax(&tmu[ti], __float_as_uint(an));
     };
 
-    unsigned long long acc[kStamps] = {};
-    unsigned long long prev = a.dbg ? __builtin_amdgcn_s_memtime() : 0ull;
-#define FPM_STAMP(i)                                                  \
-    if (a.dbg) {                                                      \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        acc[i] += now_ - prev;                                        \
-        prev = now_;                                                  \
-    }
+    FPM_STAMPS_BEGIN()
     for (int it = 0; it < a.n_order; ++it) {
         const LedPos lp = lt.at(it);
         const int led = lp.led, xc = lp.xc, yc = lp.yc;
@@ -330,7 +325,7 @@ __global__ void __launch_bounds__(f90::NT, 1) k_fused_s90(FusedS90Args a) {
         float omax = cm;
         if (dm > cm) {  // block-uniform
             for (int k = w; k < a.nbt; k += NW) {
-                if (!((dirty[k >> 5] >> (k & 31)) & 1u) || !(tmx[k] > cm)) continue;  // wave-uniform
+                if (!tile_dirty(dirty, k) || !(tmx[k] > cm)) continue;  // wave-uniform
                 const int ty = a.bty0 + band_dy(k), tx = a.btx0 + k - band_dy(k) * a.nbx;
                 float mm = 0.f;
                 // the tile's four loads issued together (clamped in bounds, masked
@@ -356,7 +351,7 @@ __global__ void __launch_bounds__(f90::NT, 1) k_fused_s90(FusedS90Args a) {
             __syncthreads();
             float m2 = 0.f;
             for (int k = tid; k < a.nbt; k += NT)
-                if (!((dirty[k >> 5] >> (k & 31)) & 1u)) m2 = fmaxf(m2, tmx[k]);
+                if (!tile_dirty(dirty, k)) m2 = fmaxf(m2, tmx[k]);
             m2 = wave_max_nonneg(m2);
             __syncthreads();
             if (lane == 0) red[w] = m2;
@@ -393,7 +388,6 @@ __global__ void __launch_bounds__(f90::NT, 1) k_fused_s90(FusedS90Args a) {
         __syncthreads();  // the last LED's red[32..]
         pm = fold_pm();
     }
-#undef FPM_STAMP
     probe.stop(st.clk);
     if (a.dbg && (tid == 0 || tid == NT - 64))
         for (int i = 0; i < kStamps; ++i) atomicAdd(&a.dbg[(tid ? kStamps : 0) + i], acc[i]);
@@ -417,42 +411,34 @@ size_t s90_lds_bytes(int nb, int nbt, int xw, int tld) {
 // Np 90 fused kernel available for this geometry (band inside the spectrum, LDS fits)?
 bool fused_s90_supported(int np, int r, const DevState &st) {
     if (np != f90::NP || r < 1 || r > f90::RMAX) return false;
-    if (st.sy0 < 0 || st.sy1 >= st.L || st.sy0 > st.sy1 || st.sx0 < 0 || st.sx1 >= st.L || st.sx0 > st.sx1)
-        return false;
-    const int bty0 = st.sy0 / kTile, btx0 = st.sx0 / kTile;
-    const int nbx = st.sx1 / kTile - btx0 + 1, nbt = nbx * (st.sy1 / kTile - bty0 + 1);
-    return s90_lds_bytes(2 * r + 1, nbt, f90::XW_DENSE, f90::TLD) <= 160 * 1024;
+    return band_valid(st) && s90_lds_bytes(2 * r + 1, band_of(st).nbt, f90::XW_DENSE, f90::TLD) <= kLdsCap;
 }
 
-hipError_t launch_fused_s90_iteration(const DevState &st, const uint16_t *meas, const int *order_dev,
-                                      const int *x0_dev, const int *y0_dev, int n_order, const float2 *tw_np,
-                                      unsigned long long *dbg, hipStream_t s) {
+hipError_t launch_fused_s90_iteration(const DevState &st, const FusedLaunch &in, hipStream_t s) {
     if (!fused_s90_supported(st.np, st.r, st)) return hipErrorInvalidValue;
     FusedS90Args a;
     a.st = st;
-    a.meas = meas;
-    a.order = order_dev;
-    a.x0 = x0_dev;
-    a.y0 = y0_dev;
-    a.tw = tw_np;
-    a.n_order = n_order;
-    a.bty0 = st.sy0 / kTile;
-    a.btx0 = st.sx0 / kTile;
-    a.nbx = st.sx1 / kTile - a.btx0 + 1;
-    a.nbt = a.nbx * (st.sy1 / kTile - a.bty0 + 1);
-    a.rnbx = 1.0f / (float)a.nbx;
+    a.meas = in.meas;
+    a.order = in.order;
+    a.x0 = in.x0;
+    a.y0 = in.y0;
+    a.tw = in.tw;
+    a.n_order = in.n_order;
+    const BandArgs bd = band_of(st);
+    a.btx0 = bd.btx0;
+    a.bty0 = bd.bty0;
+    a.nbx = bd.nbx;
+    a.nbt = bd.nbt;
+    a.rnbx = bd.rnbx;
+    a.dbg = in.dbg;
     // the conflict-light layout when it fits (FPM_S90_DENSE=1 forces the dense one)
-    const bool fast = !getenv("FPM_S90_DENSE") && s90_lds_bytes(st.nb, a.nbt, f90::XW_FAST, f90::TLD_FAST) <= 160 * 1024;
+    const bool fast = !getenv("FPM_S90_DENSE") && s90_lds_bytes(st.nb, a.nbt, f90::XW_FAST, f90::TLD_FAST) <= kLdsCap;
     a.xw = fast ? f90::XW_FAST : f90::XW_DENSE;
     for (int i = 0; i < f90::GPW; ++i) a.xg[i] = fast ? f90::XG_FAST[i] : i * f90::XT;
     a.tld = fast ? f90::TLD_FAST : f90::TLD;
-    a.dbg = dbg;
     size_t lds;  // the kernel's own LDS + the LED table when it fits
-    a.ledtab_off = ledtab_offset(s90_lds_bytes(st.nb, a.nbt, a.xw, a.tld), n_order, st.L, 160 * 1024, lds);
-    hipError_t e = hipFuncSetAttribute((const void *)k_fused_s90, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fused_s90, dim3(st.B), dim3(f90::NT), lds, s, a);
-    return hipGetLastError();
+    a.ledtab_off = ledtab_offset(s90_lds_bytes(st.nb, a.nbt, a.xw, a.tld), in.n_order, st.L, kLdsCap, lds);
+    return launch_lds(k_fused_s90, st.B, f90::NT, lds, &a, s);
 }
 
 }  // namespace fpm

@@ -24,16 +24,22 @@
 // so the amplitude step reads it in the column-major order of the buffer.
 #include <hip/hip_runtime.h>
 
+#ifndef FPM_SMALL_STAMPS
+#define FPM_SMALL_STAMPS 0  // 1: phase stamps (FPM_STAMPS=1); compiled out by default (register pressure)
+#endif
+#define FPM_STAMPS_ON FPM_SMALL_STAMPS
+
 #include "cpk.hpp"
 #include "fft_lds.hpp"
 #include "fpm_state.hpp"
+#include "fused_host.hpp"
+#include "fused_sync.hpp"
+#include "launch.hpp"
+#include "tilemax.hpp"
 #include "update.hpp"
 
 namespace fpm {
 
-#ifndef FPM_SMALL_STAMPS
-#define FPM_SMALL_STAMPS 0  // 1: phase stamps (FPM_STAMPS=1); compiled out by default (register pressure)
-#endif
 
 namespace fs {
 constexpr int NT = 1024;
@@ -49,8 +55,7 @@ struct SmallArgs {
     const float2 *tw;       // exp(-2 pi i k / Np), k < Np
     FftPlan pl;             // mixed-radix plan of Np (the generic instance)
     int n_order;
-    int btx0, bty0, nbx, nbt;  // live-band tiles (fpm_fused.hip FusedArgs)
-    float rnbx;
+    BandArgs band;             // live-band tiles (tilemax.hpp)
     unsigned long long *dbg;   // FPM_STAMPS=1 phase cycles, else null
 };
 
@@ -71,22 +76,22 @@ __global__ void __launch_bounds__(fs::NT, 1) k_fused_small(SmallArgs a) {
 #define FPM_SMALL_FFT(INV, x, y, C)                                                        \
     (NPC == 90 ? stockham_t<INV, 90, 1, 10, 9>((x), (y), (C), twl, tid, NT) \
                : stockham<INV>((x), (y), (C), a.pl, twl, tid, NT))
-    unsigned *dirty = (unsigned *)(tmx + a.nbt);       // band-tile dirty bits
-    float *red = (float *)(dirty + ((a.nbt + 31) >> 5));  // 3 x 16: per-wave maxima
+    unsigned *dirty = (unsigned *)(tmx + a.band.nbt);       // band-tile dirty bits
+    float *red = (float *)(dirty + ((a.band.nbt + 31) >> 5));  // 3 x 16: per-wave maxima
     uint16_t *ims = (uint16_t *)(red + 48);               // Np 90: staged measurement image
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, b = blockIdx.x;
     constexpr int NW = NT / 64;
-    const int nwords = (a.nbt + 31) >> 5;
+    const int nwords = (a.band.nbt + 31) >> 5;
 
     for (int i = tid; i < Np; i += NT) twl[i] = a.tw[i];
-    auto band_dy = [&](int k) { return (int)(((float)k + 0.5f) * a.rnbx); };
+    auto band_dy = [&](int k) { return (int)(((float)k + 0.5f) * a.band.rnbx); };
     auto band_gtile = [&](int k) {
         const int dy = band_dy(k);
-        return (a.bty0 + dy) * st.ntx + a.btx0 + (k - dy * a.nbx);
+        return (a.band.bty0 + dy) * st.ntx + a.band.btx0 + (k - dy * a.band.nbx);
     };
     float *tmax_g = st.tmax + (size_t)b * st.ntx * st.nty;
     unsigned *dirty_g = st.tdirty + (size_t)b * ((st.ntx * st.nty + 31) / 32);
-    for (int k = tid; k < a.nbt; k += NT) tmx[k] = tmax_g[band_gtile(k)];
+    for (int k = tid; k < a.band.nbt; k += NT) tmx[k] = tmax_g[band_gtile(k)];
     for (int i = tid; i < nwords; i += NT) dirty[i] = dirty_g[i];
 
     float2 *spec = st.spec + (size_t)b * L * L;
@@ -127,21 +132,14 @@ __global__ void __launch_bounds__(fs::NT, 1) k_fused_small(SmallArgs a) {
 
     unsigned *tmu = (unsigned *)tmx;
     auto note = [&](int py, int px, float ao, float an) {  // fpm_fused.hip: exact incremental tile maxima
-        const int ti = ((py >> 4) - a.bty0) * a.nbx + ((px >> 4) - a.btx0);
+        const int ti = ((py >> 4) - a.band.bty0) * a.band.nbx + ((px >> 4) - a.band.btx0);
         const unsigned cur = tmu[ti];
         if (an < ao && cur <= __float_as_uint(ao)) atomicOr(&dirty[ti >> 5], 1u << (ti & 31));
         if (__float_as_uint(an) > cur) atomicMax(&tmu[ti], __float_as_uint(an));
     };
     auto fidx = [&](int k) { return k < 0 ? k + Np : k; };  // FFT index of frequency k, |k| < Np
 
-    unsigned long long acc[kStamps] = {};
-    unsigned long long prev = (FPM_SMALL_STAMPS && a.dbg) ? __builtin_amdgcn_s_memtime() : 0ull;
-#define FPM_STAMP(i)                                                  \
-    if (FPM_SMALL_STAMPS && a.dbg) {                                  \
-        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
-        acc[i] += now_ - prev;                                        \
-        prev = now_;                                                  \
-    }
+    FPM_STAMPS_BEGIN()
     // Np 90: each LED's image is staged in LDS (ims) -- loaded into mreg one
     // LED ahead (with the next window's O), stored with the gather -- so the
     // amplitude step does not wait on HBM latency (7.1k -> 2.2k cycles per LED)
@@ -289,8 +287,8 @@ __global__ void __launch_bounds__(fs::NT, 1) k_fused_small(SmallArgs a) {
 
         // ---- exact max|objF| (:460,467) from the band-tile maxima
         float cm = 0.f, dm = 0.f;
-        for (int k = tid; k < a.nbt; k += NT) {
-            const bool d = (dirty[k >> 5] >> (k & 31)) & 1u;
+        for (int k = tid; k < a.band.nbt; k += NT) {
+            const bool d = tile_dirty(dirty, k);
             if (d) dm = fmaxf(dm, tmx[k]);
             else cm = fmaxf(cm, tmx[k]);
         }
@@ -310,9 +308,9 @@ __global__ void __launch_bounds__(fs::NT, 1) k_fused_small(SmallArgs a) {
         }
         float omax = cm;
         if (dm > cm) {  // block-uniform
-            for (int k = w; k < a.nbt; k += NW) {
-                if (!((dirty[k >> 5] >> (k & 31)) & 1u) || !(tmx[k] > cm)) continue;  // wave-uniform
-                const int ty = a.bty0 + band_dy(k), tx = a.btx0 + k - band_dy(k) * a.nbx;
+            for (int k = w; k < a.band.nbt; k += NW) {
+                if (!tile_dirty(dirty, k) || !(tmx[k] > cm)) continue;  // wave-uniform
+                const int ty = a.band.bty0 + band_dy(k), tx = a.band.btx0 + k - band_dy(k) * a.band.nbx;
                 float mm = 0.f;
                 // the tile's four loads issued together (clamped in bounds, masked
                 // after): a conditional load waited for each in turn
@@ -336,8 +334,8 @@ __global__ void __launch_bounds__(fs::NT, 1) k_fused_small(SmallArgs a) {
             }
             __syncthreads();
             float m2 = 0.f;
-            for (int k = tid; k < a.nbt; k += NT)
-                if (!((dirty[k >> 5] >> (k & 31)) & 1u)) m2 = fmaxf(m2, tmx[k]);
+            for (int k = tid; k < a.band.nbt; k += NT)
+                if (!tile_dirty(dirty, k)) m2 = fmaxf(m2, tmx[k]);
             m2 = wave_max_nonneg(m2);
             __syncthreads();
             if (lane == 0) red[w] = m2;
@@ -364,7 +362,6 @@ __global__ void __launch_bounds__(fs::NT, 1) k_fused_small(SmallArgs a) {
         pm = sqrtf(pm2);
         FPM_STAMP(6)
     }
-#undef FPM_STAMP
 #undef FPM_SMALL_FFT
     if (FPM_SMALL_STAMPS && a.dbg && (tid == 0 || tid == NT - 64))
         for (int i = 0; i < kStamps; ++i) atomicAdd(&a.dbg[(tid ? kStamps : 0) + i], acc[i]);
@@ -372,24 +369,13 @@ __global__ void __launch_bounds__(fs::NT, 1) k_fused_small(SmallArgs a) {
 #pragma unroll
     for (int i = 0; i < SP; ++i)
         if ((inm >> i) & 1) pup[tid + NT * i] = P[i];
-    for (int k = tid; k < a.nbt; k += NT) tmax_g[band_gtile(k)] = tmx[k];
+    for (int k = tid; k < a.band.nbt; k += NT) tmax_g[band_gtile(k)] = tmx[k];
     for (int i = tid; i < nwords; i += NT) dirty_g[i] = dirty[i];
     if (tid == 0) st.pmax[b] = pm;
 }
 
 // ------------------------------------------------------------------ host side
 namespace {
-struct SmallBand {
-    int bty0, btx0, nbx, nbt;
-};
-SmallBand small_band(const DevState &st) {
-    SmallBand b;
-    b.bty0 = st.sy0 / kTile;
-    b.btx0 = st.sx0 / kTile;
-    b.nbx = st.sx1 / kTile - b.btx0 + 1;
-    b.nbt = b.nbx * (st.sy1 / kTile - b.bty0 + 1);
-    return b;
-}
 size_t small_lds_bytes(int np, int nbt) {
     return (size_t)(2 * np * np + np) * sizeof(float2) + (size_t)nbt * sizeof(float) +
            (size_t)(nbt + 31) / 32 * sizeof(unsigned) + 48 * sizeof(float) +
@@ -401,42 +387,26 @@ size_t small_lds_bytes(int np, int nbt) {
 bool fused_small_supported(int np, int r, const DevState &st) {
     if (np < 8 || np > fs::NPMAX || r < 1 || 2 * r + 1 > np) return false;
     if ((2 * r + 1) * (2 * r + 1) > fs::NT * fs::SP) return false;
-    if (st.sy0 < 0 || st.sy1 >= st.L || st.sy0 > st.sy1 || st.sx0 < 0 || st.sx1 >= st.L || st.sx0 > st.sx1)
-        return false;
-    return small_lds_bytes(np, small_band(st).nbt) <= 160 * 1024;
+    return band_valid(st) && small_lds_bytes(np, band_of(st).nbt) <= kLdsCap;
 }
 
-hipError_t launch_fused_small_iteration(const DevState &st, const uint16_t *meas, const int *order_dev,
-                                        const int *x0_dev, const int *y0_dev, int n_order, const float2 *tw_np,
-                                        const FftPlan &pl, unsigned long long *dbg, hipStream_t s) {
+hipError_t launch_fused_small_iteration(const DevState &st, const FusedLaunch &in, const FftPlan &pl,
+                                        hipStream_t s) {
     if (!fused_small_supported(st.np, st.r, st)) return hipErrorInvalidValue;
     SmallArgs a;
     a.st = st;
-    a.meas = meas;
-    a.order = order_dev;
-    a.x0 = x0_dev;
-    a.y0 = y0_dev;
-    a.tw = tw_np;
+    a.meas = in.meas;
+    a.order = in.order;
+    a.x0 = in.x0;
+    a.y0 = in.y0;
+    a.tw = in.tw;
     a.pl = pl;
-    a.dbg = dbg;
-    a.n_order = n_order;
-    const SmallBand bd = small_band(st);
-    a.bty0 = bd.bty0;
-    a.btx0 = bd.btx0;
-    a.nbx = bd.nbx;
-    a.nbt = bd.nbt;
-    a.rnbx = 1.0f / (float)a.nbx;
-    const size_t lds = small_lds_bytes(st.np, a.nbt);
+    a.dbg = in.dbg;
+    a.n_order = in.n_order;
+    a.band = band_of(st);
     // Np 90 (configs 1/2): the instance with the transform fixed at compile time
-    const bool c90 = st.np == 90;
-    const void *fn = c90 ? (const void *)k_fused_small<90> : (const void *)k_fused_small<0>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (c90)
-        hipLaunchKernelGGL(k_fused_small<90>, dim3(st.B), dim3(fs::NT), lds, s, a);
-    else
-        hipLaunchKernelGGL(k_fused_small<0>, dim3(st.B), dim3(fs::NT), lds, s, a);
-    return hipGetLastError();
+    return launch_lds(st.np == 90 ? k_fused_small<90> : k_fused_small<0>, st.B, fs::NT,
+                      small_lds_bytes(st.np, a.band.nbt), &a, s);
 }
 
 }  // namespace fpm

@@ -4,6 +4,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "fpm_state.hpp"
+
 namespace fpm {
 
 // Handoff between the two workgroups of a patch (split mode).  Everything the
@@ -113,6 +115,28 @@ struct ClockProbe {
         }
     }
 };
+
+// Diagnostic phase stamps (FPM_STAMPS=1, a.dbg non-null) of the fused kernels:
+// shader-clock cycles per phase, summed over the LEDs of a launch
+// (wave-uniform; phases: see the stamp names of api.cpp).  Statements on the
+// kernel's own locals, not a struct: with one these kernels' register
+// allocation moved.  FPM_STAMPS_BEGIN() declares acc[] and
+// prev in the kernel's scope, FPM_STAMP(i) charges the cycles since the
+// previous stamp to phase i; both read a.dbg of the kernel argument, which
+// must be named a.  The kernel adds acc[] to a.dbg itself.  A file that
+// defines FPM_STAMPS_ON as 0 before including this header compiles them out.
+#ifndef FPM_STAMPS_ON
+#define FPM_STAMPS_ON 1  // 0 compiles the stamps out
+#endif
+#define FPM_STAMPS_BEGIN()                 \
+    unsigned long long acc[kStamps] = {}; \
+    unsigned long long prev = (FPM_STAMPS_ON && a.dbg) ? __builtin_amdgcn_s_memtime() : 0ull;
+#define FPM_STAMP(i)                                                  \
+    if (FPM_STAMPS_ON && a.dbg) {                                     \
+        const unsigned long long now_ = __builtin_amdgcn_s_memtime(); \
+        acc[i] += now_ - prev;                                        \
+        prev = now_;                                                  \
+    }
 
 // measurement stream: read once per LED, so load it non-temporally and keep
 // L2 for the spectrum window the next LED re-reads

@@ -26,6 +26,7 @@
 
 #include "fft_lds.hpp"
 #include "fpm_state.hpp"
+#include "launch.hpp"
 
 namespace fpm {
 

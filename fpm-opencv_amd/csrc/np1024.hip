@@ -37,6 +37,7 @@
 #include "cpk.hpp"
 #include "dftL.hpp"
 #include "fpm_state.hpp"
+#include "launch.hpp"
 
 #include <algorithm>
 #include <cstdlib>

@@ -38,6 +38,7 @@
 #include "cpk.hpp"
 #include "dftL.hpp"
 #include "fpm_state.hpp"
+#include "launch.hpp"
 
 #include <algorithm>
 

@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch.hpp"
+
 namespace fpm {
 
 namespace {

@@ -17,8 +17,19 @@
 #include <hip/hip_runtime.h>
 
 #include "fft_lds.hpp"
+#include "fpm_state.hpp"
 
 namespace fpm {
+
+// Tiles of the spectrum's live band (fpm_state.hpp): every other tile is
+// exactly 0 and never changes, so the fused kernels keep maxima and dirty
+// bits for these nbt tiles only (band tile k = (bty0 + k / nbx, btx0 + k % nbx));
+// st.tdirty holds the band-indexed bits between launches.  Part of every fused
+// kernel's arguments (fused_host.hpp band_of).
+struct BandArgs {
+    int btx0, bty0, nbx, nbt;
+    float rnbx;  // 1 / nbx
+};
 
 // band-tile rectangle of an LED window (band coordinates, inclusive)
 struct TileWin {
@@ -44,7 +55,7 @@ __device__ __forceinline__ void outside_max(const float *tmx, const unsigned *di
                                             const TileWin &wn, int k0, int stride, float &c, float &d) {
     float cc = 0.f, dd = 0.f;
     for (int k = k0; k < nbt; k += stride) {
-        const int dy = (int)(((float)k + 0.5f) * rnbx);  // exact for k < 2^16 (fpm_fused.hip band_dy)
+        const int dy = (int)(((float)k + 0.5f) * rnbx);  // exact for k < 2^16 (the kernels' band_dy)
         if (wn.has(dy, k - dy * nbx)) continue;
         const float v = tmx[k];
         if (tile_dirty(dirty, k)) dd = fmaxf(dd, v);

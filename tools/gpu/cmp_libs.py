@@ -16,9 +16,12 @@ G256 = (256, 768, 33, 3, 60)  # Np, L, r, LED grid side, step: metric-like, tail
 CASES = [  # (name, environment, geometry)
     ("one_workgroup", {"FPM_NO_DIST": "1", "FPM_NO_SPLIT": "1"}, G256),
     ("split_ks2", {"FPM_NO_DIST": "1", "FPM_SPLIT": "2"}, G256),
+    ("split_ks4", {"FPM_NO_DIST": "1", "FPM_SPLIT": "4"}, G256),
     ("dist_ks4", {"FPM_DIST": "4"}, G256),
     ("dist_ks8", {"FPM_DIST": "8"}, G256),
     ("np90_s90", {}, (90, 360, 30, 5, 24)),       # k_fused_s90 (configs 1 / 2)
+    ("np90_small", {"FPM_NO_S90": "1"}, (90, 360, 30, 5, 24)),  # k_fused_small<90>
+    ("np64_small", {}, (64, 256, 20, 3, 16)),     # k_fused_small<0>, the runtime plan
     ("np200_mr", {}, (200, 600, 26, 5, 40)),      # k_fused_mr (config 3)
     # the general path's Np 1024 register kernels + K4 + the L 4096 objCrop
     # passes (config 5 shape at L 2048 / 4096, fp16 spectrum storage: flag 2)
