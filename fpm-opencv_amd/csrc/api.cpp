@@ -110,6 +110,34 @@ bool make_plan(int n, FftPlan *pl) {
     return m == 1 && k < 24;
 }
 
+// Every environment switch of the library, read once per
+// context by fpm_create: a setenv between two runs never changes the kernels
+// of a live context.
+Switches read_switches() {
+    auto on = [](const char *name) { return getenv(name) != nullptr; };
+    auto num = [](const char *name) {  // the value, clamped at 0; -1 = unset
+        const char *e = getenv(name);
+        return e ? std::max(0, atoi(e)) : -1;
+    };
+    Switches sw{};
+    sw.no_s90 = on("FPM_NO_S90");
+    sw.no_reg1024 = on("FPM_NO_REG1024");
+    sw.no_reg256 = on("FPM_NO_REG256");
+    sw.t32 = on("FPM_T32");
+    sw.stamps = on("FPM_STAMPS");
+    sw.no_graph = on("FPM_NO_GRAPH");
+    sw.no_wave_cols = on("FPM_NO_WAVE_COLS");
+    sw.no_crop4k = on("FPM_NO_CROP4K");
+    sw.s90_dense = on("FPM_S90_DENSE");
+    sw.mr_dense = on("FPM_MR_DENSE");
+    sw.no_split = on("FPM_NO_SPLIT");
+    sw.no_dist = on("FPM_NO_DIST");
+    sw.patch_groups = num("FPM_PATCH_GROUPS");
+    sw.split = num("FPM_SPLIT");
+    sw.dist = num("FPM_DIST");
+    return sw;
+}
+
 std::vector<float2> twiddles(int n) {
     std::vector<float2> t(n);
     for (int k = 0; k < n; ++k) {
@@ -154,6 +182,7 @@ struct fpm_ctx {
     hipStream_t stream = nullptr;
     hipStream_t own_stream = nullptr;
     DevState st{};
+    Switches sw{};                  // the environment at fpm_create
     int path = FPM_PATH_GENERAL;
     int support_px = 0;
     FftPlan pl_np{}, pl_L{};
@@ -192,6 +221,7 @@ struct fpm_ctx {
     hipGraphExec_t led_graph_exec[kMaxGroups] = {};
     hipStream_t gstream[kMaxGroups] = {};
     hipEvent_t gfork = nullptr, gjoin[kMaxGroups] = {};
+    GeneralPlan gplan[kMaxGroups] = {};  // what each group's LED step launches (plan_general_step)
 };
 
 namespace {
@@ -228,6 +258,12 @@ void free_all(fpm_ctx *c) {
     if (c->gfork) (void)hipEventDestroy(c->gfork);
     c->gfork = nullptr;
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+}
+
+// patch group g = patches [g B / G, (g + 1) B / G)
+DevState group_view(const fpm_ctx *c, int g) {
+    const int G = c->ngroups, B = c->st.B;
+    return G == 1 ? c->st : patch_view(c->st, g * B / G, (g + 1) * B / G - g * B / G);
 }
 
 int validate(const fpm_problem *p) {
@@ -309,6 +345,8 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
     fpm_ctx *c = new fpm_ctx();
     c->prob = *prob;
     c->device = device;
+    c->sw = read_switches();
+    const Switches &sw = c->sw;
     c->order.assign(prob->order, prob->order + prob->n_order);
     c->x0.assign(prob->crop_x0, prob->crop_x0 + prob->n_stack);
     c->y0.assign(prob->crop_y0, prob->crop_y0 + prob->n_stack);
@@ -376,7 +414,7 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
     // selects the generic small-patch kernel
     const Kernel fused = fused_threads(np, r, L, st)                                  ? Kernel::Np256
                          : fused_mr_supported(np, r, st)                              ? Kernel::Np200
-                         : !getenv("FPM_NO_S90") && fused_s90_supported(np, r, st)    ? Kernel::Np90
+                         : !sw.no_s90 && fused_s90_supported(np, r, st)               ? Kernel::Np90
                          : fused_small_supported(np, r, st)                           ? Kernel::Small
                                                                                       : Kernel::General;
     const bool fused_ok = fused != Kernel::General;
@@ -407,9 +445,9 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
     // transposed; Np 256 beyond the fused kernels' radius: register kernels
     // reading the fused column layout (g = 16).  Their row IDFT writes one
     // max|P| partial per box row
-    const bool reg1024 = c->path == FPM_PATH_GENERAL && np1024_supported(np, r) && !getenv("FPM_NO_REG1024");
+    const bool reg1024 = c->path == FPM_PATH_GENERAL && np1024_supported(np, r) && !sw.no_reg1024;
     const bool reg256 =
-        c->path == FPM_PATH_GENERAL && np256_supported(np, r, L, fp16) && !getenv("FPM_NO_REG256");
+        c->path == FPM_PATH_GENERAL && np256_supported(np, r, L, fp16) && !sw.no_reg256;
     st.npart = (c->path == FPM_PATH_GENERAL) ? (reg1024 || reg256 ? std::max(pupil_parts(nb), nb) : pupil_parts(nb))
                                              : 1;
     if ((rc = dalloc(c, &st.pmax, (size_t)B * st.npart))) return fail(rc);
@@ -424,7 +462,7 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
         // fp16 spectrum storage on the Np 1024 register kernels: the row /
         // column scratch T block-scaled in fp16 too (half its HBM traffic;
         // FPM_T32=1 keeps it fp32)
-        if (reg1024 && fp16 && !getenv("FPM_T32")) {
+        if (reg1024 && fp16 && !sw.t32) {
             if ((rc = dalloc(c, &st.T16, (size_t)B * nb * np))) return fail(rc);
             if ((rc = dalloc(c, &st.tsr, (size_t)B * nb))) return fail(rc);
             if ((rc = dalloc(c, &st.tsc, (size_t)B * np))) return fail(rc);
@@ -440,8 +478,7 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
         // and for the Np 256 register kernels, whose three short launches per
         // LED then overlap one group's tail with the other's start (dataset_mono
         // at Np 256, 64 patches: 1.18 -> 1.25 M LED-updates/s)
-        const char *pg = getenv("FPM_PATCH_GROUPS");
-        c->ngroups = pg ? atoi(pg) : (reg1024 || reg256 ? 2 : 1);
+        c->ngroups = sw.patch_groups >= 0 ? sw.patch_groups : (reg1024 || reg256 ? 2 : 1);
         c->ngroups = std::max(1, std::min({c->ngroups, B, (int)fpm_ctx::kMaxGroups}));
         for (int g = 1; g < c->ngroups; ++g) {
             if (hipStreamCreateWithFlags(&c->gstream[g], hipStreamNonBlocking) != hipSuccess ||
@@ -459,9 +496,9 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
         // (fused_dist.hip), else split mode (column parts only), else one
         // workgroup per patch
         if (c->kernel == Kernel::Np256) {
-            const int dks = fused_dist_parts(B, n_cu, r, L);
+            const int dks = fused_dist_parts(B, n_cu, r, L, sw);
             if (dks > 1) c->kernel = Kernel::Np256Dist;
-            c->split_ks = dks > 1 ? dks : fused_split_parts(c->row().threads, B, n_cu);
+            c->split_ks = dks > 1 ? dks : fused_split_parts(c->row().threads, B, n_cu, sw);
         }
         if (c->split_ks > 1) {
             const size_t nx = c->kernel == Kernel::Np256Dist ? fused_dist_elems(B, c->split_ks)
@@ -484,7 +521,7 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
             return fail(set_err(FPM_ERR_DEVICE, "memset failed"));
         st.clk = c->clk;
     }
-    if (getenv("FPM_STAMPS") && c->path == FPM_PATH_FUSED) {
+    if (sw.stamps && c->path == FPM_PATH_FUSED) {
         if ((rc = dalloc(c, &c->dbg, 2 * kStamps))) return fail(rc);
         if (hipMemset(c->dbg, 0, 2 * kStamps * sizeof(unsigned long long)) != hipSuccess)
             return fail(set_err(FPM_ERR_DEVICE, "memset failed"));
@@ -500,6 +537,12 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
         hipMemcpy(c->x0_dev, c->x0.data(), c->x0.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(c->y0_dev, c->y0.data(), c->y0.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
         return fail(set_err(FPM_ERR_DEVICE, "table upload failed"));
+    if (c->path == FPM_PATH_GENERAL)
+        for (int g = 0; g < c->ngroups; ++g) {
+            DevState v = group_view(c, g);
+            v.meas_g = c->meas_g;  // the layout the stack has once it is uploaded
+            c->gplan[g] = plan_general_step(v, c->pl_np, sw);
+        }
     *out = c;
     return FPM_OK;
 }
@@ -631,21 +674,16 @@ namespace {
         if (e_ != hipSuccess) return e_;             \
     } while (0)
 
-// patch group g = patches [g B / G, (g + 1) B / G)
-DevState group_view(const fpm_ctx *c, int g) {
-    const int G = c->ngroups, B = c->st.B;
-    return G == 1 ? c->st : patch_view(c->st, g * B / G, (g + 1) * B / G - g * B / G);
-}
-
 // one group's LED chain of an iteration on stream s
-hipError_t launch_group_chain(const fpm_ctx *c, const DevState &v, hipStream_t s) {
+hipError_t launch_group_chain(const fpm_ctx *c, int g, hipStream_t s) {
+    const DevState v = group_view(c, g);
     for (int i = 0; i < c->prob.n_order; ++i) {
         const int led = c->order[i];
-        HIP_RET(launch_general_step(v, led, c->x0[led], c->y0[led], c->pl_np, c->tw_np, i == 0, s));
+        HIP_RET(launch_general_step(c->gplan[g], v, led, c->x0[led], c->y0[led], c->tw_np, i == 0, s));
     }
     // Np 1024 / 256 register kernels: the last LED's pupil commit (the others
     // are folded into the next LED's row IDFT)
-    if (commit_folded(v)) HIP_RET(launch_pupil_commit(v, s));
+    if (c->gplan[g].commit_folded()) HIP_RET(launch_pupil_commit(v, s));
     return hipSuccess;
 }
 
@@ -677,10 +715,10 @@ hipError_t launch_general_iteration(fpm_ctx *c, hipStream_t s) {
     for (int i = 0; i < c->prob.n_order; ++i) {
         const int led = c->order[i];
         for (int g = 0; g < G; ++g)
-            HIP_RET(launch_general_step(view[g], led, c->x0[led], c->y0[led], c->pl_np, c->tw_np, i == 0,
+            HIP_RET(launch_general_step(c->gplan[g], view[g], led, c->x0[led], c->y0[led], c->tw_np, i == 0,
                                         group_stream(c, g, s)));
     }
-    if (commit_folded(c->st))
+    if (c->gplan[0].commit_folded())
         for (int g = 0; g < G; ++g) HIP_RET(launch_pupil_commit(view[g], group_stream(c, g, s)));
     return join_groups(c, s);
 }
@@ -694,7 +732,7 @@ int general_graph(fpm_ctx *c) {
     for (int g = 0; g < c->ngroups; ++g) {
         hipStream_t cs = group_stream(c, g, c->own_stream);
         HIP_TRY(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        hipError_t e = launch_group_chain(c, group_view(c, g), cs);
+        hipError_t e = launch_group_chain(c, g, cs);
         hipGraph_t gr = nullptr;
         hipError_t e2 = hipStreamEndCapture(cs, &gr);
         if (e == hipSuccess) e = e2;
@@ -746,12 +784,13 @@ int fpm_run(fpm_ctx *c, int iters) {
         HIP_TRY(hipEventCreate(&e));
         c->evpool.push_back(e);
     }
-    const bool use_graph = c->path != FPM_PATH_FUSED && iters > 0 && !getenv("FPM_NO_GRAPH");
+    const bool use_graph = c->path != FPM_PATH_FUSED && iters > 0 && !c->sw.no_graph;
     if (use_graph) {
         const int r = general_graph(c);
         if (r != FPM_OK) return r;
     }
-    const FusedLaunch in{c->meas, c->order_dev, c->x0_dev, c->y0_dev, c->prob.n_order, c->tw_np, c->dbg};
+    const FusedLaunch in{c->meas, c->order_dev, c->x0_dev, c->y0_dev, c->prob.n_order, c->tw_np, c->dbg,
+                         c->kernel == Kernel::Np90 ? c->sw.s90_dense : c->sw.mr_dense};
     hipEvent_t *ev = c->evpool.data();
     HIP_TRY(hipEventRecord(ev[0], c->stream));
     for (int it = 0; it < iters; ++it) {
@@ -775,7 +814,7 @@ int fpm_run(fpm_ctx *c, int iters) {
         }
         HIP_TRY(hipEventRecord(ev[2 + 3 * it], c->stream));
         if (!last_only || it == iters - 1) {
-            HIP_TRY(launch_objcrop(c->st, c->objcrop, c->pl_L, c->tw_L, c->stream));
+            HIP_TRY(launch_objcrop(c->st, c->objcrop, c->pl_L, c->tw_L, c->sw, c->stream));
             c->objcrop_valid = true;
         }
         HIP_TRY(hipEventRecord(ev[3 + 3 * it], c->stream));
@@ -884,7 +923,7 @@ int fpm_download(fpm_ctx *c, float *objF, float *objCrop, float *pupil, float *s
         }
     }
     if (objCrop) {
-        if (!c->objcrop_valid) HIP_TRY(launch_objcrop(c->st, c->objcrop, c->pl_L, c->tw_L, c->stream));
+        if (!c->objcrop_valid) HIP_TRY(launch_objcrop(c->st, c->objcrop, c->pl_L, c->tw_L, c->sw, c->stream));
         c->objcrop_valid = true;
         HIP_TRY(hipStreamSynchronize(c->stream));
         HIP_TRY(hipMemcpy(objCrop, c->objcrop, B * ll * sizeof(float2), hipMemcpyDeviceToHost));
@@ -918,7 +957,7 @@ int fpm_download_objcrop_device(fpm_ctx *c, float *dst) {
     if (!c || !dst) return set_err(FPM_ERR_INVAL, "null argument");
     if (!c->initialized) return set_err(FPM_ERR_STATE, "download before fpm_init");
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->objcrop_valid) HIP_TRY(launch_objcrop(c->st, c->objcrop, c->pl_L, c->tw_L, c->stream));
+    if (!c->objcrop_valid) HIP_TRY(launch_objcrop(c->st, c->objcrop, c->pl_L, c->tw_L, c->sw, c->stream));
     c->objcrop_valid = true;
     const size_t n = (size_t)c->st.B * c->st.L * c->st.L * sizeof(float2);
     HIP_TRY(hipMemcpyAsync(dst, c->objcrop, n, hipMemcpyDeviceToDevice, c->stream));

@@ -322,6 +322,16 @@ __device__ __forceinline__ float2 *stockham_t_ld(const LD &ld, float2 *a, float2
     }
 }
 
+// Orders one wave's LDS accesses around a point all its lanes reach (LDS
+// operations of one wave execute in issue order; the fence pair keeps the
+// compiler from moving them): the wave-private transforms synchronise with
+// this instead of a block barrier.
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 // ---- block reductions -------------------------------------------------------
 // Max over the 64 lanes, in every lane; the wave must be fully active.  DPP
 // moves within each row of 16 (xor 1 and 2 as quad permutes, then the

@@ -771,11 +771,11 @@ size_t fused_flag_words(int B, int ks) { return 2 * (size_t)ks * B + 1; }
 // checks the grid against the occupancy query): KS = 4 when 4 B <= CUs, KS = 2
 // when 2 B <= CUs, else 1.  FPM_NO_SPLIT=1 disables it; FPM_SPLIT=1/2/4 forces
 // a part count where the grid still fits.
-int fused_split_parts(int nt, int B, int n_cu) {
-    if (nt != 512 || B < 1 || getenv("FPM_NO_SPLIT")) return 1;
+int fused_split_parts(int nt, int B, int n_cu, const Switches &sw) {
+    if (nt != 512 || B < 1 || sw.no_split) return 1;
     auto fits = [&](int ks) { return 8 * ks * ((B + 7) / 8) <= n_cu; };
-    if (const char *e = getenv("FPM_SPLIT")) {
-        const int ks = atoi(e);
+    if (sw.split >= 0) {
+        const int ks = sw.split;
         return (ks == 2 || ks == 4) && fits(ks) ? ks : 1;
     }
     return fits(4) ? 4 : fits(2) ? 2 : 1;

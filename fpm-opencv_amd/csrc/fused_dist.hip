@@ -748,13 +748,13 @@ size_t fused_dist_elems(int B, int ks) { return (size_t)B * dist_patch_elems(ks)
 // mode (7.17 vs 6.71 ms: T crosses the L2 four times per LED), so KS = 2 is
 // only used when forced.  FPM_NO_DIST=1 disables it; FPM_DIST=2/4/8 forces
 // a count that fits.
-int fused_dist_parts(int B, int n_cu, int r, int L) {
-    if (B < 1 || getenv("FPM_NO_DIST")) return 0;
+int fused_dist_parts(int B, int n_cu, int r, int L, const Switches &sw) {
+    if (B < 1 || sw.no_dist) return 0;
     const FusedGeom g = fused_geometry(fz::NP, r);
     if (!g.ok || L % kTile) return 0;
     auto fits = [&](int ks) { return 8 * ks * ((B + 7) / 8) <= n_cu; };
-    if (const char *e = getenv("FPM_DIST")) {
-        const int ks = atoi(e);
+    if (sw.dist >= 0) {
+        const int ks = sw.dist;
         return (ks == 2 || ks == 4 || ks == 8) && fits(ks) ? ks : 0;
     }
     return fits(8) ? 8 : fits(4) ? 4 : 0;

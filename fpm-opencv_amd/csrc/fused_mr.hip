@@ -33,8 +33,6 @@
 //      (:405-475), as in fpm_fused.hip.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "cpk.hpp"
 #include "dft200.hpp"
 #include "fft_lds.hpp"
@@ -461,8 +459,7 @@ hipError_t launch_fused_mr_iteration(const DevState &st, const FusedLaunch &in, 
     a.dbg = in.dbg;
     // bank-friendly strides while LDS allows: tiles first, then the T pitch
     // (FPM_MR_DENSE=1 forces the dense layout, test_gpu_fused_mr.py)
-    const bool dense = getenv("FPM_MR_DENSE") != nullptr;
-    auto fits = [&](int xw, int tld) { return !dense && mr_lds_bytes(st.nb, a.band.nbt, xw, tld) <= kLdsCap; };
+    auto fits = [&](int xw, int tld) { return !in.dense && mr_lds_bytes(st.nb, a.band.nbt, xw, tld) <= kLdsCap; };
     a.tld = fits(fm::XW_STRIDE, fm::TLD_FAST) ? fm::TLD_FAST : fm::TLD;
     a.xw = fits(fm::XW_SHIFT, a.tld) ? fm::XW_SHIFT : fits(fm::XW_STRIDE, a.tld) ? fm::XW_STRIDE : fm::XW_DENSE;
     for (int i = 0; i < fm::GPW; ++i)

@@ -25,8 +25,6 @@
 // box row in registers (kx = fold(l + 10 k)).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "cpk.hpp"
 #include "dft90.hpp"
 #include "fft_lds.hpp"
@@ -432,7 +430,7 @@ hipError_t launch_fused_s90_iteration(const DevState &st, const FusedLaunch &in,
     a.rnbx = bd.rnbx;
     a.dbg = in.dbg;
     // the conflict-light layout when it fits (FPM_S90_DENSE=1 forces the dense one)
-    const bool fast = !getenv("FPM_S90_DENSE") && s90_lds_bytes(st.nb, a.nbt, f90::XW_FAST, f90::TLD_FAST) <= kLdsCap;
+    const bool fast = !in.dense && s90_lds_bytes(st.nb, a.nbt, f90::XW_FAST, f90::TLD_FAST) <= kLdsCap;
     a.xw = fast ? f90::XW_FAST : f90::XW_DENSE;
     for (int i = 0; i < f90::GPW; ++i) a.xg[i] = fast ? f90::XG_FAST[i] : i * f90::XT;
     a.tld = fast ? f90::TLD_FAST : f90::TLD;

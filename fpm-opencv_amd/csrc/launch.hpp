@@ -1,5 +1,6 @@
-// launch.hpp -- every host function of the .hip files that api.cpp calls.
-// Included by api.cpp and by each file that defines one of them, so a
+// launch.hpp -- every host function of the .hip files that api.cpp or another
+// .hip file calls, and the host structs they exchange.
+// Included by api.cpp and by each file that defines or calls one of them, so a
 // signature that drifts is a compile error and not a link-time surprise.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,33 +11,80 @@
 
 namespace fpm {
 
-// ---- general path (general.hip)
-hipError_t launch_general_step(const DevState &st, int led, int x0, int y0, const FftPlan &pl,
+// ---- the environment switches, read once per context (read_switches, api.cpp)
+struct Switches {
+    bool no_s90, no_reg1024, no_reg256, t32;  // FPM_NO_S90, FPM_NO_REG1024, FPM_NO_REG256, FPM_T32
+    bool stamps, no_graph;                    // FPM_STAMPS, FPM_NO_GRAPH
+    bool no_wave_cols, no_crop4k;             // FPM_NO_WAVE_COLS, FPM_NO_CROP4K
+    bool s90_dense, mr_dense;                 // FPM_S90_DENSE, FPM_MR_DENSE
+    bool no_split, no_dist;                   // FPM_NO_SPLIT, FPM_NO_DIST
+    int patch_groups, split, dist;            // FPM_PATCH_GROUPS, FPM_SPLIT, FPM_DIST: the value (>= 0), -1 = unset
+};
+
+// ---- general path: the LED step (general.hip)
+// One launch of the LDS step kernels (K1 / K2 / K3): every kernel takes
+// (DevState, StepArgs, FftPlan, twiddles) and the tiled / wave ones one int more.
+struct StepKernel {
+    const void *fn;
+    dim3 grid, block;
+    size_t lds;  // dynamic LDS bytes
+    int arg;     // rows per block lr, columns per block lc (both log2) or the column pitch P
+};
+// What launch_general_step launches for a context (a patch group): nothing in
+// it depends on the LED, so fpm_create makes it once (plan_general_step).
+struct GeneralPlan {
+    enum Kind { Reg1024, Reg256, Lds } kind;  // np1024.hip / np256.hip register kernels, or K1-K3 below
+    FftPlan pl;                               // of Np
+    StepKernel k1, k2, k3;                    // Lds only
+    // the register row / column kernels fold the pupil commit into the next
+    // LED's row IDFT (launch_pupil_commit after the iteration's last LED)
+    bool commit_folded() const { return kind != Lds; }
+};
+GeneralPlan plan_general_step(const DevState &st, const FftPlan &pl, const Switches &sw);
+// first: the iteration's first LED (register kernels: no pupil commit pending)
+hipError_t launch_general_step(const GeneralPlan &plan, const DevState &st, int led, int x0, int y0,
                                const float2 *tw, bool first, hipStream_t s);
 hipError_t launch_pupil_commit(const DevState &st, hipStream_t s);
-int fft_max_len();
 int pupil_parts(int nb);
+// Np 1024 / Np 256 register row/column kernels of the general path (np1024.hip, np256.hip)
+bool np1024_supported(int np, int r);
+bool np256_supported(int np, int r, int L, bool fp16);
+hipError_t launch_np1024_rows_cols(const DevState &st, const StepArgs &sa, const float2 *tw, bool commit,
+                                   hipStream_t s);
+hipError_t launch_np256_rows_cols(const DevState &st, const StepArgs &sa, const float2 *tw, bool commit,
+                                  hipStream_t s);
+
+// ---- batched transform of any length 2^a 3^b 5^c (fft_batch.hip)
+// Input band: sequences gs outside [qlo, qhi] and elements gi with
+// (gi + eroll) mod n outside [elo, ehi] are known to be exactly zero and are
+// not read (objCrop over the spectrum's live band, fpm_state.hpp); the default
+// covers everything.
+struct FftBand {
+    int qlo = 0, qhi = 0x7fffffff, elo = 0, ehi = 0x7fffffff, eroll = 0;
+};
+int fft_max_len();
+hipError_t launch_fft_batch(bool inverse, const float2 *in, float2 *out, const FftPlan &pl, const float2 *tw,
+                            int nseq, int B, size_t in_bs, int in_ss, int in_es, size_t out_bs, int out_ss,
+                            int out_es, int sroll, int iroll, float scale, hipStream_t s,
+                            const __half2 *in16 = nullptr, float in16_scale = 1.f, FftBand band = FftBand());
+
+// ---- fpm_init (init.hip) and objCrop (objcrop.hip)
 hipError_t launch_init(const DevState &st, int init_led, float2 *scratch, const FftPlan &pl_np,
                        const float2 *tw_np, hipStream_t s);
 hipError_t launch_objcrop(const DevState &st, float2 *out, const FftPlan &pl_L, const float2 *tw_L,
-                          hipStream_t s);
-// Np 1024 / Np 256 register row/column kernels of the general path
-// (np1024.hip, np256.hip; both fold the pupil commit into the next LED)
-bool np1024_supported(int np, int r);
-bool np256_supported(int np, int r, int L, bool fp16);
-bool commit_folded(const DevState &st);
+                          const Switches &sw, hipStream_t s);
 
 // ---- Np 256 fused kernel: one workgroup per patch and split mode (fpm_fused.hip)
 int fused_threads(int np, int r, int L, const DevState &st);
 size_t fused_T_elems(int np, int r, int B);
 size_t fused_xch_elems(int B, int ks);
 size_t fused_flag_words(int B, int ks);
-int fused_split_parts(int nt, int B, int n_cu);
+int fused_split_parts(int nt, int B, int n_cu, const Switches &sw);
 hipError_t launch_fused_iteration(const DevState &st, const FusedLaunch &in, int ks, float2 *xch, int *flags,
                                   int stall_led, hipStream_t s);
 // ---- distributed mode of the Np 256 kernel (fused_dist.hip)
 size_t fused_dist_elems(int B, int ks);
-int fused_dist_parts(int B, int n_cu, int r, int L);
+int fused_dist_parts(int B, int n_cu, int r, int L, const Switches &sw);
 hipError_t launch_fused_dist(const DevState &st, const FusedLaunch &in, int ks, float2 *area, int *flags,
                              int stall_led, unsigned tag_base, hipStream_t s);
 // ---- Np 200 fused kernel (fused_mr.hip)

@@ -38,9 +38,9 @@
 #include "dftL.hpp"
 #include "fpm_state.hpp"
 #include "launch.hpp"
+#include "update.hpp"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace fpm {
 
@@ -63,12 +63,6 @@ static_assert(4 * 8 * CXP <= WTILE, "cross-group tile");
 // half a row at a time (all of it measured slower, 36.4 -> 40.0 us).
 
 namespace {
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ float2 w1024(const float2 *twL, int e, bool inv) {
     const float2 w = twL[e & (n1k::N - 1)];
@@ -499,14 +493,9 @@ __global__ void __launch_bounds__(n1k::NT) k_rows1024_fwd(DevState st, StepArgs 
             const int kx = fold(t + 16 * (4 * c + bb) + 256 * p);
             if (kx * kx > w2) continue;
             const size_t si = srow + kx;
-            const float2 o = ov[i];                              // pre-update Objfcrop (:361)
-            const float2 pp = pv[i];
-            const float2 D = csub(x[4 * p + bb], cmul(o, pp));   // Objfup - ObjfcropP (:409,463)
-            const float pa = cmag(pp);                           // object update (:406-419,433)
-            const float2 dpc = cmul(cmul(D, cscale(cconj(pp), pa)), upd_coef_div(pa * pa + st.delta2, st.d2_im, pm));
-            spec_st(st, b, si, cadd(o, dpc));
-            const float oa = cmag(o);                            // pupil numerator (:459-464,469)
-            dP[kx] = cmul(cmul(D, cscale(cconj(o), oa)), upd_coef_div(oa * oa + st.delta1, st.d1_im, 1.0f));
+            float2 num;
+            spec_st(st, b, si, general_update(x[4 * p + bb], ov[i], pv[i], pm, st, num));
+            dP[kx] = num;
         }
     }
 }

@@ -310,6 +310,8 @@ __global__ void __launch_bounds__(n256::NT) __attribute__((amdgpu_waves_per_eu(4
             for (int k = 0; k < 8; ++k) {
                 const int kx = fold256(t + 16 * (8 * hp + k));
                 if (kx * kx > w2) continue;
+                // general_update (update.hpp) written out: with the spectrum store after the
+                // numerator instead of between the two, this kernel schedules one instruction more
                 const float2 o = ov[k];                                 // pre-update Objfcrop (:361)
                 const float2 p = pp[k];
                 const float2 D = csub(F[8 * hp + k], cmul(o, p));       // Objfup - ObjfcropP (:409,463)

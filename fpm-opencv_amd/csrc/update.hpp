@@ -1,5 +1,6 @@
-// update.hpp -- the per-pixel object update and pupil numerator shared by
-// the fused LED-update kernels (fpm_fused.hip, fused_mr.hip).
+// update.hpp -- the per-pixel arithmetic of an LED step: the object update and
+// pupil numerator of the fused LED-update kernels (slot_update) and of the
+// general path (general_update), and the general path's amplitude replacement.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,6 +42,33 @@ __device__ __forceinline__ float2 slot_update(float2 f, float2 o, float2 p, floa
     const float sp = sp0 * fp, so = so0 * fo;
     num = pout(pmul(dq, (pf2){so, -qo * so}));
     return pout(po + pmul(dp, (pf2){sp, -qp * sp}));
+}
+
+// The same update in the general path (general.hip, np1024.hip, np256.hip),
+// with IEEE divisions (upd_coef_div): F = Objfup (:394), o = the pre-update
+// Objfcrop (:361).  Returns O', writes the pupil numerator to num.
+__device__ __forceinline__ float2 general_update(float2 F, float2 o, float2 p, float pm, const DevState &st,
+                                                 float2 &num) {
+    const float2 D = csub(F, cmul(o, p));  // Objfup - ObjfcropP (:409,463)
+    // object update (:406-419,433): D |P| P* / ((|P|^2 + d2) max|P|)
+    const float pa = cmag(p);
+    const float2 dpc = cmul(cmul(D, cscale(cconj(p), pa)), upd_coef_div(pa * pa + st.delta2, st.d2_im, pm));
+    // pupil numerator (:459-464,469): D |O| O* / (|O|^2 + d1); max|objF| at the commit
+    const float oa = cmag(o);
+    num = cmul(cmul(D, cscale(cconj(o), oa)), upd_coef_div(oa * oa + st.delta1, st.d1_im, 1.0f));
+    return cadd(o, dpc);
+}
+
+// Amplitude replacement of one pixel (fpmMain.cpp:378-393): v = the unscaled
+// IDFT value, psi = v / Np^2, I the measured intensity;
+// psi' = sqrt(I) psi / |psi + eps| (eps on Re and Im)
+__device__ __forceinline__ float2 amp_replace(float2 v, float inv_n2, uint16_t I, const DevState &st) {
+    const float2 psi = cscale(v, inv_n2);
+    const float a = sqrtf((float)I);
+    const float tre = psi.x + st.eps, tim = psi.y + st.eps_im;
+    const float mag = sqrtf(tre * tre + tim * tim);
+    const float sc = a / mag;
+    return make_float2(psi.x * sc, psi.y * sc);
 }
 
 }  // namespace fpm

@@ -23,7 +23,7 @@ int fpm_debug_slot_update(const float *f, const float *o, const float *p, const 
                           float delta2, float d1_im, float d2_im, float *nv, float *num, float *oa);
 
 /* The general path's update coefficient f / ((a + i c) m) (fpm_state.hpp
- * upd_coef_div, general.hip / np1024.hip) for n host inputs; out[2k], out[2k+1]
+ * upd_coef_div, called by update.hpp general_update) for n host inputs; out[2k], out[2k+1]
  * = real, imaginary part. */
 int fpm_debug_update_coef(const float *a, const float *c, const float *m, const float *f, float *out, int n);
 

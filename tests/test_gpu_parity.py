@@ -45,6 +45,27 @@ def test_single_patch_matches_oracle(case):
     np.testing.assert_array_equal(out["support"][0], ref["support"].real.astype(np.float32))
 
 
+def test_one_sequence_row_kernels_match_oracle():
+    """Np 2700 = 2^2 3^3 5^2 is the smallest size at which two box rows do not
+    fit a 256-thread tile, so the row passes run one row per block
+    (k_gather_rowifft, k_rowfft_update); the column pass is
+    k_colpass_tiled<512, 16> and objCrop (L 3000) the batched transform with
+    two sequences per block.  Two LEDs, one iteration."""
+    # measured before these kernels were first touched: rel L2 objF 3.6e-7,
+    # objCrop 3.7e-7, pupil 3.0e-7 -- a 2700-point fp32 transform stays far
+    # inside the file's one-iteration bound
+    Np, L, r = 2700, 3000, 4
+    x0, y0, order = np.array([150, 50]), np.array([150, 150]), [0, 1]
+    stack = make_stack(Np, L, r, x0, y0, n_patch=1)
+    ref = oracle_run(stack[:, 0], order, x0, y0, Np, L, r, 5, 10, 1)
+    prob = fpm_amd.Problem(Np, L, order, x0, y0, r, 5, 10, n_patch=1, path=fpm_amd.PATH_GENERAL)
+    out = fpm_amd.run_fpm(prob, stack, 1)
+    err = {k: rel_l2(out[k][0], ref[k]) for k in ("objF", "objCrop", "pupil")}
+    print("Np 2700 rel L2:", " ".join(f"{k} {v:.3e}" for k, v in err.items()))
+    for k, v in err.items():
+        assert v < _tol(1), k
+
+
 def test_batched_patches_are_independent():
     """B patches in one context == each patch run alone through the oracle."""
     Np, L, r, iters = 32, 96, 6, 2

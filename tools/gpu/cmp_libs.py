@@ -27,6 +27,17 @@ CASES = [  # (name, environment, geometry)
     # passes (config 5 shape at L 2048 / 4096, fp16 spectrum storage: flag 2)
     ("np1024_fp16", {"CMP_FLAGS": "2", "CMP_NPATCH": "1"}, (1024, 4096, 333, 3, 200)),
     ("np1024_fp32", {"CMP_NPATCH": "2"}, (1024, 2048, 120, 3, 100)),
+    # the general path's LDS kernels and its launch plan (CMP_PATH: the requested path)
+    ("np32_wave_cols", {"CMP_PATH": "general", "CMP_NPATCH": "2"}, (32, 96, 6, 5, 4)),  # tiled rows, wave columns,
+                                                                                         # batched objCrop
+    ("np32_tiled_cols", {"CMP_PATH": "general", "CMP_NPATCH": "2", "FPM_NO_WAVE_COLS": "1"}, (32, 96, 6, 5, 4)),
+    ("np256_reg", {"CMP_NPATCH": "2"}, (256, 768, 84, 3, 60)),                          # Np 256 register kernels
+    ("np256_lds", {"CMP_NPATCH": "2", "FPM_NO_REG256": "1"}, (256, 768, 84, 3, 60)),    # LDS kernels at Np 256
+    ("np256_direct", {"CMP_NPATCH": "2", "FPM_NO_GRAPH": "1", "FPM_PATCH_GROUPS": "2"},  # direct launches across groups
+     (256, 768, 84, 3, 60)),
+    ("np1024_lds", {"CMP_NPATCH": "1", "FPM_NO_REG1024": "1"}, (1024, 2048, 120, 3, 100)),  # LDS kernels at Np 1024
+    # the one-sequence row kernels (two box rows do not fit a 256-thread tile)
+    ("np2700_one_seq", {"CMP_PATH": "general", "CMP_NPATCH": "1"}, (2700, 3000, 4, 2, 100)),
 ]
 
 CHILD = r"""
@@ -39,7 +50,10 @@ x0, y0, order = grid_geometry(Np, L, nside, step)
 import os
 npatch = int(os.environ.get("CMP_NPATCH", "4"))
 stack = make_stack(Np, L, r, x0, y0, n_patch=npatch, seed=7)
-prob = fpm_amd.Problem(Np, L, order, x0, y0, r, 5, 10, n_patch=npatch, flags=int(os.environ.get("CMP_FLAGS", "0")))
+path = {"auto": fpm_amd.PATH_AUTO, "general": fpm_amd.PATH_GENERAL, "fused": fpm_amd.PATH_FUSED}[
+    os.environ.get("CMP_PATH", "auto")]
+prob = fpm_amd.Problem(Np, L, order, x0, y0, r, 5, 10, n_patch=npatch, path=path,
+                       flags=int(os.environ.get("CMP_FLAGS", "0")))
 out = fpm_amd.run_fpm(prob, stack, 2)
 np.savez(sys.argv[1], **{k: np.asarray(out[k]) for k in ("objF", "objCrop", "pupil")})
 """
