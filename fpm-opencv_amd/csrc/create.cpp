@@ -1,0 +1,381 @@
+// create.cpp -- fpm_create and fpm_destroy: validate the problem, check the
+// device, plan the context (plan_context: every decision, no HIP call), then
+// allocate what the plan names and upload the tables.  The context owns what
+// it created: its destructor releases it, on fpm_destroy and on every failed
+// fpm_create alike.
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+
+#include "ctx.hpp"
+
+using namespace fpm;
+
+fpm_ctx::~fpm_ctx() {
+    drop_graphs();
+    for (void *p : allocs) (void)hipFree(p);
+    for (auto e : evpool) (void)hipEventDestroy(e);
+    for (int g = 0; g < kMaxGroups; ++g) {
+        if (gstream[g]) (void)hipStreamDestroy(gstream[g]);
+        if (gjoin[g]) (void)hipEventDestroy(gjoin[g]);
+    }
+    if (gfork) (void)hipEventDestroy(gfork);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+}
+
+void fpm_ctx::drop_graphs() {
+    for (int g = 0; g < kMaxGroups; ++g) {
+        if (led_graph_exec[g]) (void)hipGraphExecDestroy(led_graph_exec[g]);
+        if (led_graph[g]) (void)hipGraphDestroy(led_graph[g]);
+        led_graph_exec[g] = nullptr;
+        led_graph[g] = nullptr;
+    }
+}
+
+namespace {
+
+bool make_plan(int n, FftPlan *pl) {
+    std::memset(pl, 0, sizeof *pl);
+    pl->n = n;
+    int m = n, k = 0;
+    while (m % 8 == 0) { pl->radix[k++] = 8; m /= 8; }
+    while (m % 4 == 0) { pl->radix[k++] = 4; m /= 4; }
+    while (m % 2 == 0) { pl->radix[k++] = 2; m /= 2; }
+    while (m % 3 == 0) { pl->radix[k++] = 3; m /= 3; }
+    while (m % 5 == 0) { pl->radix[k++] = 5; m /= 5; }
+    pl->nstages = k;
+    return m == 1 && k < 24;
+}
+
+// Every environment switch of the library, read once per
+// context by fpm_create: a setenv between two runs never changes the kernels
+// of a live context.
+Switches read_switches() {
+    auto on = [](const char *name) { return getenv(name) != nullptr; };
+    auto num = [](const char *name) {  // the value, clamped at 0; -1 = unset
+        const char *e = getenv(name);
+        return e ? std::max(0, atoi(e)) : -1;
+    };
+    Switches sw{};
+    sw.no_s90 = on("FPM_NO_S90");
+    sw.no_reg1024 = on("FPM_NO_REG1024");
+    sw.no_reg256 = on("FPM_NO_REG256");
+    sw.t32 = on("FPM_T32");
+    sw.stamps = on("FPM_STAMPS");
+    sw.no_graph = on("FPM_NO_GRAPH");
+    sw.no_wave_cols = on("FPM_NO_WAVE_COLS");
+    sw.no_crop4k = on("FPM_NO_CROP4K");
+    sw.s90_dense = on("FPM_S90_DENSE");
+    sw.mr_dense = on("FPM_MR_DENSE");
+    sw.no_split = on("FPM_NO_SPLIT");
+    sw.no_dist = on("FPM_NO_DIST");
+    sw.patch_groups = num("FPM_PATCH_GROUPS");
+    sw.split = num("FPM_SPLIT");
+    sw.dist = num("FPM_DIST");
+    return sw;
+}
+
+std::vector<float2> twiddles(int n) {
+    std::vector<float2> t(n);
+    for (int k = 0; k < n; ++k) {
+        const double a = -2.0 * M_PI * (double)k / (double)n;
+        t[k] = make_float2((float)std::cos(a), (float)std::sin(a));
+    }
+    return t;
+}
+
+int validate(const fpm_problem *p) {
+    if (!p) return set_err(FPM_ERR_INVAL, "null problem");
+    if (p->np < 4 || (p->np & 1)) return set_err(FPM_ERR_INVAL, "Np=%d must be even and >= 4", p->np);
+    if (p->nlarge < p->np || (p->nlarge & 1))
+        return set_err(FPM_ERR_INVAL, "Nlarge=%d must be even and >= Np", p->nlarge);
+    FftPlan t;
+    if (!make_plan(p->np, &t)) return set_err(FPM_ERR_INVAL, "Np=%d is not 2^a 3^b 5^c", p->np);
+    if (!make_plan(p->nlarge, &t)) return set_err(FPM_ERR_INVAL, "Nlarge=%d is not 2^a 3^b 5^c", p->nlarge);
+    if (p->nlarge > fft_max_len())
+        return set_err(FPM_ERR_INVAL, "Nlarge=%d exceeds the batched transform limit %d", p->nlarge, fft_max_len());
+    if (p->na_radius < 0 || 2 * p->na_radius + 1 > p->np)
+        return set_err(FPM_ERR_INVAL, "naRadius=%d needs 2r+1 <= Np=%d", p->na_radius, p->np);
+    if (p->n_stack < 1 || p->n_order < 2)
+        return set_err(FPM_ERR_INVAL, "need n_stack>=1 and ledUsedCount>=2 (init uses sortedIndicies.at(1))");
+    if (!p->order || !p->crop_x0 || !p->crop_y0) return set_err(FPM_ERR_INVAL, "null order/crop arrays");
+    if (p->init_pos < 0 || p->init_pos >= p->n_order) return set_err(FPM_ERR_INVAL, "init_pos out of range");
+    if (!(p->delta2 > 0.0))
+        return set_err(FPM_ERR_INVAL, "delta2=%g: the reference divides 0/0 outside the support when delta2==0",
+                       p->delta2);
+    if (!(p->delta1 > 0.0)) return set_err(FPM_ERR_INVAL, "delta1=%g must be > 0", p->delta1);
+    if (p->n_patch < 1) return set_err(FPM_ERR_INVAL, "n_patch=%d", p->n_patch);
+    for (int i = 0; i < p->n_order; ++i)
+        if (p->order[i] < 0 || p->order[i] >= p->n_stack)
+            return set_err(FPM_ERR_INVAL, "order[%d]=%d outside the stack", i, p->order[i]);
+    for (int i = 0; i < p->n_stack; ++i) {
+        // cv::Rect(cropXStart, cropYStart, Np, Np) must lie inside objF (fpmMain.cpp:361)
+        if (p->crop_x0[i] < 0 || p->crop_x0[i] > p->nlarge - p->np || p->crop_y0[i] < 0 ||
+            p->crop_y0[i] > p->nlarge - p->np)
+            return set_err(FPM_ERR_INVAL, "LED %d crop (%d,%d) leaves the %dx%d spectrum", i, p->crop_x0[i],
+                           p->crop_y0[i], p->nlarge, p->nlarge);
+    }
+    return FPM_OK;
+}
+
+// a gfx950 device; makes it current and reports its CU count
+int check_device(int device, int *n_cu) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return set_err(FPM_ERR_NODEV, "no HIP device visible");
+    if (device < 0 || device >= ndev) return set_err(FPM_ERR_NODEV, "device %d of %d", device, ndev);
+    hipDeviceProp_t pr;
+    HIP_TRY(hipGetDeviceProperties(&pr, device));
+    if (std::strncmp(pr.gcnArchName, "gfx950", 6) != 0)
+        return set_err(FPM_ERR_NODEV, "device %d is %s, this library is built for gfx950", device, pr.gcnArchName);
+    HIP_TRY(hipSetDevice(device));
+    *n_cu = pr.multiProcessorCount;
+    return FPM_OK;
+}
+
+// the DevState scalars of the validated problem c->prob
+void plan_state(fpm_ctx *c) {
+    const fpm_problem &p = c->prob;
+    const int np = p.np, L = p.nlarge, r = p.na_radius;
+    DevState &st = c->st;
+    st.np = np;
+    st.L = L;
+    st.r = r;
+    st.nb = 2 * r + 1;
+    st.B = st.mB = p.n_patch;
+    st.ntx = st.nty = (L + kTile - 1) / kTile;
+    st.delta1 = (float)p.delta1;
+    st.delta2 = (float)p.delta2;
+    st.eps = (float)p.eps;
+    // cv::add(UMat CV_64FC2, double) semantics (fpm_hip.h FPM_FLAG_SCALAR_RE_ONLY)
+    const bool re_only = (p.flags & FPM_FLAG_SCALAR_RE_ONLY) != 0;
+    st.eps_im = re_only ? 0.f : st.eps;
+    st.d1_im = re_only ? 0.f : st.delta1;
+    st.d2_im = re_only ? 0.f : st.delta2;
+    // fp16 storage scale: 2^-ceil(log2 Np^2) (fpm_state.hpp)
+    int e2 = 0;
+    while ((1ll << e2) < (long long)np * np) ++e2;
+    st.hscale = std::ldexp(1.0f, -e2);
+    st.hinv = std::ldexp(1.0f, e2);
+    // live band of the centred spectrum (fpm_state.hpp): the init placement at
+    // L/2 (fpmMain.cpp:332-343) and every used LED's support box (:405-447)
+    st.sy0 = st.sx0 = L / 2 - r;
+    st.sy1 = st.sx1 = L / 2 + r;
+    for (int i = 0; i < p.n_order; ++i) {
+        const int led = c->order[i];
+        st.sy0 = std::min(st.sy0, c->y0[led] + np / 2 - r);
+        st.sy1 = std::max(st.sy1, c->y0[led] + np / 2 + r);
+        st.sx0 = std::min(st.sx0, c->x0[led] + np / 2 - r);
+        st.sx1 = std::max(st.sx1, c->x0[led] + np / 2 + r);
+    }
+    st.sy0 = std::max(st.sy0, 0);
+    st.sx0 = std::max(st.sx0, 0);
+    st.sy1 = std::min(st.sy1, L - 1);
+    st.sx1 = std::min(st.sx1, L - 1);
+}
+
+// Everything a context is, decided from the validated problem (c->prob with
+// its arrays), the switches (c->sw) and the device's CU count before anything
+// is created: no HIP call, no device memory.  Refuses a fused path that this
+// geometry or fp16 spectrum storage does not have.
+int plan_context(fpm_ctx *c, int n_cu) {
+    const fpm_problem &p = c->prob;
+    const Switches &sw = c->sw;
+    const int np = p.np, L = p.nlarge, r = p.na_radius, nb = 2 * r + 1, B = p.n_patch;
+    DevState &st = c->st;
+    plan_state(c);
+    make_plan(np, &c->pl_np);
+    make_plan(L, &c->pl_L);
+
+    // support disk on the box: Euclidean disk == filled cv::circle (fpmMain.cpp:307)
+    c->disk.resize((size_t)nb * nb);
+    for (int i = 0; i < nb; ++i)
+        for (int j = 0; j < nb; ++j) {
+            const int ky = i - r, kx = j - r;
+            c->disk[(size_t)i * nb + j] = (ky * ky + kx * kx <= r * r) ? 1 : 0;
+            c->support_px += c->disk[(size_t)i * nb + j];
+        }
+
+    const bool fp16 = (p.flags & FPM_FLAG_SPEC_FP16) != 0;
+    // Np 90 (configs 1 / 2): the register-transform kernel unless FPM_NO_S90=1
+    // selects the generic small-patch kernel
+    const Kernel fused = fused_threads(np, r, L, st)                                  ? Kernel::Np256
+                         : fused_mr_supported(np, r, st)                              ? Kernel::Np200
+                         : !sw.no_s90 && fused_s90_supported(np, r, st)               ? Kernel::Np90
+                         : fused_small_supported(np, r, st)                           ? Kernel::Small
+                                                                                      : Kernel::General;
+    if (p.path == FPM_PATH_FUSED && (fp16 || fused == Kernel::General))
+        return set_err(FPM_ERR_INVAL, "fused path unsupported for Np=%d r=%d L=%d%s", np, r, L,
+                       fp16 ? " with fp16 spectrum storage" : "");
+    c->kernel = (p.path == FPM_PATH_GENERAL || fp16) ? Kernel::General : fused;
+
+    if (c->fused()) {
+        // small batches: every phase distributed over KS workgroups per patch
+        // (fused_dist.hip), else split mode (column parts only), else one
+        // workgroup per patch
+        if (c->kernel == Kernel::Np256) {
+            const int dks = fused_dist_parts(B, n_cu, r, L, sw);
+            if (dks > 1) c->kernel = Kernel::Np256Dist;
+            c->split_ks = dks > 1 ? dks : fused_split_parts(c->row().threads, B, n_cu, sw);
+        }
+        st.npart = 1;
+        c->meas_g = c->row().meas_g < 0 ? np : c->row().meas_g;
+        return FPM_OK;
+    }
+    // Np 1024 general path: register row/column kernels reading the stack
+    // transposed; Np 256 beyond the fused kernels' radius: register kernels
+    // reading the fused column layout (g = 16).  Their row IDFT writes one
+    // max|P| partial per box row
+    c->general_kind = np1024_supported(np, r) && !sw.no_reg1024           ? GeneralPlan::Reg1024
+                      : np256_supported(np, r, L, fp16) && !sw.no_reg256  ? GeneralPlan::Reg256
+                                                                          : GeneralPlan::Lds;
+    const bool reg = c->general_kind != GeneralPlan::Lds;
+    st.npart = reg ? std::max(pupil_parts(nb), nb) : pupil_parts(nb);
+    c->meas_g = c->general_kind == GeneralPlan::Reg1024 ? np : c->general_kind == GeneralPlan::Reg256 ? 16 : 0;
+    // fp16 spectrum storage on the Np 1024 register kernels: the row /
+    // column scratch T block-scaled in fp16 too (half its HBM traffic;
+    // FPM_T32=1 keeps it fp32)
+    c->t16 = c->general_kind == GeneralPlan::Reg1024 && fp16 && !sw.t32;
+    // patch groups on concurrent streams (FPM_PATCH_GROUPS=n overrides):
+    // two for the Np 1024 kernels, whose row launches cover a few patches
+    // in 1.3 rounds of workgroups (config 5, 8 patches: 65.5 -> 57.5 ms of
+    // LED steps per iteration; 3 or 4 groups measured slower, 79 / 77 ms),
+    // and for the Np 256 register kernels, whose three short launches per
+    // LED then overlap one group's tail with the other's start (dataset_mono
+    // at Np 256, 64 patches: 1.18 -> 1.25 M LED-updates/s)
+    c->ngroups = sw.patch_groups >= 0 ? sw.patch_groups : (reg ? 2 : 1);
+    c->ngroups = std::max(1, std::min({c->ngroups, B, (int)fpm_ctx::kMaxGroups}));
+    return FPM_OK;
+}
+
+// device memory of the context, counted in fpm_info.device_bytes and freed by
+// the destructor; zero: cleared as well
+template <typename T>
+int dalloc(fpm_ctx *c, T **p, size_t count, bool zero) {
+    void *q = nullptr;
+    const size_t nb = count * sizeof(T);
+    hipError_t e = hipMalloc(&q, nb > 0 ? nb : 16);
+    if (e != hipSuccess) return set_err(FPM_ERR_NOMEM, "hipMalloc(%zu) failed: %s", nb, hipGetErrorString(e));
+    c->allocs.push_back(q);
+    c->bytes += nb;
+    *p = (T *)q;
+    if (zero && hipMemset(q, 0, nb) != hipSuccess) return set_err(FPM_ERR_DEVICE, "memset failed");
+    return FPM_OK;
+}
+
+// the run stream, the buffers and the patch groups' streams the plan names
+int allocate(fpm_ctx *c) {
+    if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess)
+        return set_err(FPM_ERR_DEVICE, "hipStreamCreate failed");
+    c->stream = c->own_stream;
+    DevState &st = c->st;
+    const size_t B = st.B, np = st.np, nb = st.nb, specn = B * st.L * st.L;
+    int rc = FPM_OK;  // of the first allocation that failed; the ones after it are skipped
+    auto get = [&](auto **p, size_t n, bool zero = false) {
+        if (rc == FPM_OK) rc = dalloc(c, p, n, zero);
+    };
+    if (c->prob.flags & FPM_FLAG_SPEC_FP16) get(&st.spec16, specn);
+    else get(&st.spec, specn);
+    get(&c->objcrop, specn);
+    get(&st.pupil, B * nb * nb);
+    get(&st.tmax, B * st.ntx * st.nty);
+    get(&st.tdirty, B * ((st.ntx * st.nty + 31) / 32));
+    get(&st.pmax, B * st.npart);
+    get(&c->disk_dev, c->disk.size());
+    get(&c->meas, stack_elems(c));
+    get(&c->order_dev, c->order.size());
+    get(&c->x0_dev, c->x0.size());
+    get(&c->y0_dev, c->y0.size());
+    if (c->fused()) {
+        get(&st.T, fused_T_elems(st.np, st.r, st.B));
+        if (c->split_ks > 1) {
+            // distributed mode's tile words start at tag 0, which no LED uses
+            get(&c->xch, c->kernel == Kernel::Np256Dist ? fused_dist_elems(st.B, c->split_ks)
+                                                        : fused_xch_elems(st.B, c->split_ks), true);
+            get(&c->split_flags, fused_flag_words(st.B, c->split_ks), true);
+        }
+        get(&c->clk, 3, true);
+        if (c->sw.stamps) get(&c->dbg, 2 * kStamps, true);
+    } else {
+        if (c->t16) {
+            get(&st.T16, B * nb * np);
+            get(&st.tsr, B * nb);
+            get(&st.tsc, B * np);
+        } else {
+            get(&st.T, B * nb * np);
+        }
+        get(&st.dP, B * nb * nb);
+        get(&st.rmax, B * st.nty);
+    }
+    get(&c->tw_np, np);
+    get(&c->tw_L, (size_t)st.L);
+    if (rc) return rc;
+    st.meas = c->meas;
+    st.disk = c->disk_dev;
+    st.clk = c->clk;
+    for (int g = 1; g < c->ngroups; ++g) {
+        if (hipStreamCreateWithFlags(&c->gstream[g], hipStreamNonBlocking) != hipSuccess ||
+            hipEventCreateWithFlags(&c->gjoin[g], hipEventDisableTiming) != hipSuccess)
+            return set_err(FPM_ERR_DEVICE, "patch-group stream / event creation failed");
+    }
+    if (c->ngroups > 1 && hipEventCreateWithFlags(&c->gfork, hipEventDisableTiming) != hipSuccess)
+        return set_err(FPM_ERR_DEVICE, "patch-group event creation failed");
+    return FPM_OK;
+}
+
+int upload_tables(fpm_ctx *c) {
+    const auto twn = twiddles(c->st.np), twl = twiddles(c->st.L);
+    auto put = [](void *dst, const auto &v) {
+        return hipMemcpy(dst, v.data(), v.size() * sizeof v[0], hipMemcpyHostToDevice) == hipSuccess;
+    };
+    if (!put(c->tw_np, twn) || !put(c->tw_L, twl) || !put(c->disk_dev, c->disk) || !put(c->order_dev, c->order) ||
+        !put(c->x0_dev, c->x0) || !put(c->y0_dev, c->y0))
+        return set_err(FPM_ERR_DEVICE, "table upload failed");
+    return FPM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
+    if (!out) return set_err(FPM_ERR_INVAL, "null out");
+    *out = nullptr;
+    int rc = validate(prob), n_cu = 0;
+    if (rc || (rc = check_device(device, &n_cu))) return rc;
+
+    std::unique_ptr<fpm_ctx> c(new fpm_ctx());
+    c->prob = *prob;
+    c->device = device;
+    c->sw = read_switches();
+    c->order.assign(prob->order, prob->order + prob->n_order);
+    c->x0.assign(prob->crop_x0, prob->crop_x0 + prob->n_stack);
+    c->y0.assign(prob->crop_y0, prob->crop_y0 + prob->n_stack);
+    c->prob.order = c->order.data();
+    c->prob.crop_x0 = c->x0.data();
+    c->prob.crop_y0 = c->y0.data();
+
+    if ((rc = plan_context(c.get(), n_cu)) || (rc = allocate(c.get())) || (rc = upload_tables(c.get()))) return rc;
+    if (!c->fused())
+        for (int g = 0; g < c->ngroups; ++g)
+            c->gplan[g] = plan_general_step(group_view(c.get(), g), c->general_kind, c->pl_np, c->sw);
+    *out = c.release();
+    return FPM_OK;
+}
+
+void fpm_destroy(fpm_ctx *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    delete c;
+}
+
+int fpm_set_stream(fpm_ctx *c, void *s) {
+    if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
+    c->stream = s ? (hipStream_t)s : c->own_stream;
+    return FPM_OK;
+}
+
+}  // extern "C"

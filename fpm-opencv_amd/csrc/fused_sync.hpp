@@ -118,7 +118,7 @@ struct ClockProbe {
 
 // Diagnostic phase stamps (FPM_STAMPS=1, a.dbg non-null) of the fused kernels:
 // shader-clock cycles per phase, summed over the LEDs of a launch
-// (wave-uniform; phases: see the stamp names of api.cpp).  Statements on the
+// (wave-uniform; phases: see the stamp names of ctx.hpp).  Statements on the
 // kernel's own locals, not a struct: with one these kernels' register
 // allocation moved.  FPM_STAMPS_BEGIN() declares acc[] and
 // prev in the kernel's scope, FPM_STAMP(i) charges the cycles since the
@@ -153,7 +153,7 @@ __device__ __forceinline__ uint4 ld_stream(const uint4 *p) {
 // "coop-launch") without the cooperative launch's per-launch host cost.
 // Two such grids must never run side by side on one device (each could get
 // only part of its blocks resident and both would wait for the rest), so
-// launch_coresident_raw (api.cpp) orders every co-resident grid of the
+// launch_coresident_raw (coresident.cpp) orders every co-resident grid of the
 // process on a device after the previous one: a per-device mutex, a wait on
 // the previous grid's completion event, a new event after the launch -- what
 // the cooperative launch's serialisation gave.  Across processes a device is

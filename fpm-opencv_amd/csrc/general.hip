@@ -584,14 +584,13 @@ static int colw_cw(const FftPlan &pl) {
 }
 
 // ---- the plan and the step launcher -------------------------------------------
-GeneralPlan plan_general_step(const DevState &st, const FftPlan &pl, const Switches &sw) {
+GeneralPlan plan_general_step(const DevState &st, GeneralPlan::Kind kind, const FftPlan &pl, const Switches &sw) {
     GeneralPlan p{};
     p.pl = pl;
     // Np 1024: register-resident row/column transforms (np1024.hip); Np 256
-    // beyond the fused kernels' radius: np256.hip, whose K4 runs inside its R2
-    p.kind = st.np == 1024 && st.meas_g == 1024 ? GeneralPlan::Reg1024
-             : st.np == 256 && st.meas_g == 16  ? GeneralPlan::Reg256
-                                                : GeneralPlan::Lds;
+    // beyond the fused kernels' radius: np256.hip, whose K4 runs inside its R2;
+    // the context's plan decides which (plan_context, create.cpp)
+    p.kind = kind;
     if (p.kind != GeneralPlan::Lds) return p;
     const int np = st.np;
     const size_t lds = 2 * (size_t)np * sizeof(float2);  // of the one-sequence kernels

@@ -1,6 +1,7 @@
-// launch.hpp -- every host function of the .hip files that api.cpp or another
-// .hip file calls, and the host structs they exchange.
-// Included by api.cpp and by each file that defines or calls one of them, so a
+// launch.hpp -- every host function of the .hip files that the extern "C"
+// boundary (ctx.hpp and the .cpp files) or another .hip file calls, and the
+// host structs they exchange.
+// Included by ctx.hpp and by each file that defines or calls one of them, so a
 // signature that drifts is a compile error and not a link-time surprise.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -11,7 +12,7 @@
 
 namespace fpm {
 
-// ---- the environment switches, read once per context (read_switches, api.cpp)
+// ---- the environment switches, read once per context (read_switches, create.cpp)
 struct Switches {
     bool no_s90, no_reg1024, no_reg256, t32;  // FPM_NO_S90, FPM_NO_REG1024, FPM_NO_REG256, FPM_T32
     bool stamps, no_graph;                    // FPM_STAMPS, FPM_NO_GRAPH
@@ -33,14 +34,17 @@ struct StepKernel {
 // What launch_general_step launches for a context (a patch group): nothing in
 // it depends on the LED, so fpm_create makes it once (plan_general_step).
 struct GeneralPlan {
-    enum Kind { Reg1024, Reg256, Lds } kind;  // np1024.hip / np256.hip register kernels, or K1-K3 below
+    // np1024.hip / np256.hip register kernels, or K1-K3 below; chosen with the
+    // rest of the context (plan_context, create.cpp), since the stack's layout
+    // and the scratch buffers follow it
+    enum Kind { Reg1024, Reg256, Lds } kind;
     FftPlan pl;                               // of Np
     StepKernel k1, k2, k3;                    // Lds only
     // the register row / column kernels fold the pupil commit into the next
     // LED's row IDFT (launch_pupil_commit after the iteration's last LED)
     bool commit_folded() const { return kind != Lds; }
 };
-GeneralPlan plan_general_step(const DevState &st, const FftPlan &pl, const Switches &sw);
+GeneralPlan plan_general_step(const DevState &st, GeneralPlan::Kind kind, const FftPlan &pl, const Switches &sw);
 // first: the iteration's first LED (register kernels: no pupil commit pending)
 hipError_t launch_general_step(const GeneralPlan &plan, const DevState &st, int led, int x0, int y0,
                                const float2 *tw, bool first, hipStream_t s);

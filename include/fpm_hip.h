@@ -150,7 +150,10 @@ typedef struct fpm_info {
 #define FPM_INFO_V3_SIZE  (offsetof(fpm_info, fused_kernel) + sizeof(int32_t))
 
 /* Per-kernel timing of the most recent fpm_run, from HIP events recorded on
- * the stream the kernels were launched on. */
+ * the stream the kernels were launched on.  fpm_run clears it (and the
+ * fpm_clock below) once its arguments are accepted, so after a run that was
+ * refused (a capturing stream) or failed every field is zero: never the values
+ * of an earlier run. */
 typedef struct fpm_timing {
     double run_ms;         /* whole fpm_run, event to event                    */
     double led_ms;         /* LED-update kernels only (all iterations)         */
@@ -227,7 +230,8 @@ int  fpm_get_timing(const fpm_ctx *ctx, fpm_timing *timing);
  * its last LED, so clock_mhz = cycles / real time is the shader clock the
  * kernel actually ran at and cycles_per_launch its length in cycles, which a
  * slower clock does not change (MI355X_MICROARCH.md, DVFS).  launches = 0 on
- * the general path, which has no probe. */
+ * the general path, which has no probe, and after an fpm_run that was refused
+ * or failed (see fpm_timing). */
 typedef struct fpm_clock {
     double clock_mhz;          /* mean shader clock over the probed launches   */
     double cycles_per_launch;  /* block 0's shader cycles per launch           */

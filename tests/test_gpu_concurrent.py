@@ -4,7 +4,7 @@ Split and distributed modes launch grids whose workgroups wait on each other,
 so every block must be resident at once (fused_sync.hpp launch_coresident).
 Two such grids from two contexts on two streams of the same GPU could each get
 only part of their blocks resident and wait for the rest until the ~1 s
-timeout; launch_coresident_raw (api.cpp) orders every co-resident grid of the
+timeout; launch_coresident_raw (coresident.cpp) orders every co-resident grid of the
 process on a device after the previous one.  The test runs two 64-patch
 contexts (k_fused_dist<4>: 256 workgroups each, one per CU) from two host
 threads at once and checks both against the same runs made one after the
@@ -104,6 +104,9 @@ def test_run_on_a_capturing_stream_is_refused():
             with torch.cuda.graph(g, stream=cs, capture_error_mode="relaxed"):
                 s.run(1)
         assert ei.value.code == fpm_amd.FPM_ERR_INVAL and "capturing" in str(ei.value)
+        # a refused run reports zeros, not the earlier run's clock and timing
+        assert s.clock().launches == 0
+        assert s.timing().led_launches == 0
         s.set_stream(None)
         s.run(1)  # the refused call left the context usable
         got = s.download(objF=False, support=False)

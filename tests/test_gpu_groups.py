@@ -1,4 +1,4 @@
-"""Patch groups of the general path (api.cpp launch_general_iteration): the
+"""Patch groups of the general path (run.cpp launch_general_iteration): the
 context's patches split into G groups whose per-LED launches run on G
 concurrent streams (FPM_PATCH_GROUPS; two by default for the Np 1024
 kernels).  Patches are independent (fpmMain.cpp:274-498 runs runFPM per

@@ -1,6 +1,6 @@
 """fpm_info of every kernel selection: the kernel code, its threads per
 workgroup and the workgroups per patch, one row per selection (the table
-api.cpp keeps per kernel)."""
+ctx.hpp keeps per kernel), and the path, which follows from the kernel."""
 import pytest
 
 import fpm_amd
@@ -33,3 +33,20 @@ def test_info_reports_the_selected_kernel(Np, L, r, path, env, want, monkeypatch
     with fpm_amd.Solver(prob) as s:
         info = s.info()
     assert (info.fused_kernel, info.threads_per_wg, info.wg_per_patch) == want
+    assert (info.path == fpm_amd.PATH_FUSED) == (info.fused_kernel != fpm_amd.KERNEL_GENERAL)
+
+
+def test_fused_path_with_fp16_storage_is_refused_before_anything_is_created():
+    """PATH_FUSED with fp16 spectrum storage has no kernel: fpm_create refuses
+    it while planning the context; PATH_AUTO takes the general path."""
+    Np, L, r = 64, 256, 20
+    x0, y0, order = grid_geometry(Np, L, 3, 20)
+
+    def problem(path):
+        return fpm_amd.Problem(Np, L, order, x0, y0, r, 10, 3, n_patch=2, path=path, flags=fpm_amd.FLAG_SPEC_FP16)
+
+    with pytest.raises(fpm_amd.FpmError) as ei:
+        fpm_amd.Solver(problem(fpm_amd.PATH_FUSED))
+    assert ei.value.code == fpm_amd.FPM_ERR_INVAL and "fused path unsupported" in str(ei.value)
+    with fpm_amd.Solver(problem(fpm_amd.PATH_AUTO)) as s:
+        assert s.info().fused_kernel == fpm_amd.KERNEL_GENERAL

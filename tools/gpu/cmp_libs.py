@@ -1,7 +1,8 @@
 """Bit-identity of two builds of libfpm_hip.so on the same inputs (same-box
 checks of changes that must not move a bit, e.g. a reduction rewritten with
 DPP moves).  Each library runs in its own process (FPM_HIP_LIB is read at
-import); the outputs are compared exactly.
+import); the outputs and the context's fpm_info (the kernel selection and the
+device bytes allocated) are compared exactly.
 
 usage: python tools/gpu/cmp_libs.py <lib_a.so> <lib_b.so>
 """
@@ -54,8 +55,15 @@ path = {"auto": fpm_amd.PATH_AUTO, "general": fpm_amd.PATH_GENERAL, "fused": fpm
     os.environ.get("CMP_PATH", "auto")]
 prob = fpm_amd.Problem(Np, L, order, x0, y0, r, 5, 10, n_patch=npatch, path=path,
                        flags=int(os.environ.get("CMP_FLAGS", "0")))
-out = fpm_amd.run_fpm(prob, stack, 2)
-np.savez(sys.argv[1], **{k: np.asarray(out[k]) for k in ("objF", "objCrop", "pupil")})
+with fpm_amd.Solver(prob) as s:
+    i = s.info()
+    s.upload(stack)
+    s.init()
+    s.run(2)
+    out = s.download()
+info = np.array([i.path, i.box, i.support_px, i.device_bytes, i.wg_per_patch, i.fused_kernel, i.threads_per_wg],
+                dtype=np.int64)  # the plan and the allocation total
+np.savez(sys.argv[1], info=info, **{k: np.asarray(out[k]) for k in ("objF", "objCrop", "pupil")})
 """
 
 
@@ -80,6 +88,8 @@ def main():
             else:  # which outputs moved, by how much (relative L2)
                 rel = {k: float(np.linalg.norm(za[k] - zb[k]) / max(np.linalg.norm(za[k]), 1e-30))
                        for k in za.files if not np.array_equal(za[k], zb[k])}
+                if "info" in rel:
+                    print(f"{name}: info {za['info'].tolist()} != {zb['info'].tolist()}")
                 print(f"{name}: DIFFERENT " + " ".join(f"{k} rel {v:.2e}" for k, v in rel.items()))
     sys.exit(0 if ok else 1)
 
