@@ -90,6 +90,14 @@ int fpm_debug_set_stall(fpm_ctx *c, int led) {
     return FPM_OK;
 }
 
+int fpm_debug_get_plan(const fpm_ctx *c, int *meas_g, int *general_kind, int *residual_kind) {
+    if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
+    if (meas_g) *meas_g = c->meas_g;
+    if (general_kind) *general_kind = c->fused() ? -1 : (int)c->general_kind;
+    if (residual_kind) *residual_kind = (int)c->rplan.kind;
+    return FPM_OK;
+}
+
 int fpm_runFPM(const fpm_problem *prob, int device, const uint16_t *meas, int iters, float *objF, float *objCrop,
                float *pupil, float *support) {
     fpm_ctx *c = nullptr;

@@ -22,6 +22,8 @@ fpm_ctx::~fpm_ctx() {
         if (gjoin[g]) (void)hipEventDestroy(gjoin[g]);
     }
     if (gfork) (void)hipEventDestroy(gfork);
+    for (auto e : res_ev)
+        if (e) (void)hipEventDestroy(e);
     if (own_stream) (void)hipStreamDestroy(own_stream);
 }
 
@@ -74,6 +76,9 @@ Switches read_switches() {
     sw.patch_groups = num("FPM_PATCH_GROUPS");
     sw.split = num("FPM_SPLIT");
     sw.dist = num("FPM_DIST");
+    sw.res_lds = on("FPM_RES_LDS");
+    sw.res_one_seq = on("FPM_RES_ONE_SEQ");
+    sw.res_batch = num("FPM_RES_BATCH");
     return sw;
 }
 
@@ -222,6 +227,7 @@ int plan_context(fpm_ctx *c, int n_cu) {
         }
         st.npart = 1;
         c->meas_g = c->row().meas_g < 0 ? np : c->row().meas_g;
+        c->rplan = plan_residual(st, c->pl_np, p.n_order, c->meas_g, fp16, sw);
         return FPM_OK;
     }
     // Np 1024 general path: register row/column kernels reading the stack
@@ -247,21 +253,7 @@ int plan_context(fpm_ctx *c, int n_cu) {
     // at Np 256, 64 patches: 1.18 -> 1.25 M LED-updates/s)
     c->ngroups = sw.patch_groups >= 0 ? sw.patch_groups : (reg ? 2 : 1);
     c->ngroups = std::max(1, std::min({c->ngroups, B, (int)fpm_ctx::kMaxGroups}));
-    return FPM_OK;
-}
-
-// device memory of the context, counted in fpm_info.device_bytes and freed by
-// the destructor; zero: cleared as well
-template <typename T>
-int dalloc(fpm_ctx *c, T **p, size_t count, bool zero) {
-    void *q = nullptr;
-    const size_t nb = count * sizeof(T);
-    hipError_t e = hipMalloc(&q, nb > 0 ? nb : 16);
-    if (e != hipSuccess) return set_err(FPM_ERR_NOMEM, "hipMalloc(%zu) failed: %s", nb, hipGetErrorString(e));
-    c->allocs.push_back(q);
-    c->bytes += nb;
-    *p = (T *)q;
-    if (zero && hipMemset(q, 0, nb) != hipSuccess) return set_err(FPM_ERR_DEVICE, "memset failed");
+    c->rplan = plan_residual(st, c->pl_np, p.n_order, c->meas_g, fp16, sw);
     return FPM_OK;
 }
 

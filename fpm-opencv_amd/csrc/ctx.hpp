@@ -3,6 +3,7 @@
 //   create.cpp    validate, plan, allocate, destroy
 //   transfer.cpp  the stack uploads and the downloads
 //   run.cpp       fpm_init, fpm_run, the general path's patch groups and graphs
+//   residual_api.cpp  fpm_residual (kernels: residual.hip)
 //   api.cpp       errors, version, info, timing, clock, fpm_runFPM
 // Errors are negative codes plus fpm_last_error(); nothing here ever falls
 // back to a CPU path.
@@ -90,6 +91,7 @@ struct fpm_ctx {
     // one group's launches fill the other's partial last round of workgroups
     int ngroups = 1;
     static constexpr int kMaxGroups = 8;
+    fpm::ResidualPlan rplan{};      // fpm_residual: kernel pair and LEDs per launch
     // ---- what the context owns
     hipStream_t stream = nullptr;   // the run stream: own_stream or the caller's (fpm_set_stream)
     hipStream_t own_stream = nullptr;
@@ -119,6 +121,14 @@ struct fpm_ctx {
     hipEvent_t gfork = nullptr, gjoin[kMaxGroups] = {};
     fpm::GeneralPlan gplan[kMaxGroups] = {};  // what each group's LED step launches (plan_general_step)
 
+    // fpm_residual's scratch, allocated by its first call: T of one batch, the
+    // per-block partials, the folded [n_order][B] sums, and its two events
+    float2 *res_T = nullptr;
+    double *res_perr = nullptr, *res_err = nullptr, *res_ref = nullptr;
+    unsigned long long *res_pref = nullptr;
+    hipEvent_t res_ev[2] = {};
+    bool res_ready = false;         // all of the above exist
+
     fpm_ctx() = default;
     fpm_ctx(const fpm_ctx &) = delete;
     fpm_ctx &operator=(const fpm_ctx &) = delete;
@@ -138,6 +148,25 @@ inline DevState group_view(const fpm_ctx *c, int g) {
     const int G = c->ngroups, B = c->st.B;
     return G == 1 ? c->st : patch_view(c->st, g * B / G, (g + 1) * B / G - g * B / G);
 }
+
+// device memory of the context, counted in fpm_info.device_bytes and freed by
+// the destructor; zero: cleared as well
+template <typename T>
+int dalloc(fpm_ctx *c, T **p, size_t count, bool zero) {
+    void *q = nullptr;
+    const size_t nb = count * sizeof(T);
+    hipError_t e = hipMalloc(&q, nb > 0 ? nb : 16);
+    if (e != hipSuccess) return set_err(FPM_ERR_NOMEM, "hipMalloc(%zu) failed: %s", nb, hipGetErrorString(e));
+    c->allocs.push_back(q);
+    c->bytes += nb;
+    *p = (T *)q;
+    if (zero && hipMemset(q, 0, nb) != hipSuccess) return set_err(FPM_ERR_DEVICE, "memset failed");
+    return FPM_OK;
+}
+
+// blocking entry points (event waits, read-backs) never run inside a capture:
+// FPM_ERR_INVAL for `what` on a capturing stream, before anything is enqueued (run.cpp)
+int refuse_capture(const fpm_ctx *c, const char *what);
 
 // the objCrop IDFT of the current spectrum (run.cpp); ensure: only when the
 // buffer does not hold it yet

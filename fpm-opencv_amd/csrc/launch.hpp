@@ -20,6 +20,9 @@ struct Switches {
     bool s90_dense, mr_dense;                 // FPM_S90_DENSE, FPM_MR_DENSE
     bool no_split, no_dist;                   // FPM_NO_SPLIT, FPM_NO_DIST
     int patch_groups, split, dist;            // FPM_PATCH_GROUPS, FPM_SPLIT, FPM_DIST: the value (>= 0), -1 = unset
+    bool res_lds;                             // FPM_RES_LDS: the residual's LDS kernel pair where the register pair applies
+    bool res_one_seq;                         // FPM_RES_ONE_SEQ: the LDS pair's one-sequence-per-block kernels at any size
+    int res_batch;                            // FPM_RES_BATCH: LEDs per residual launch (> 0), else from the scratch cap
 };
 
 // ---- general path: the LED step (general.hip)
@@ -57,6 +60,42 @@ hipError_t launch_np1024_rows_cols(const DevState &st, const StepArgs &sa, const
                                    hipStream_t s);
 hipError_t launch_np256_rows_cols(const DevState &st, const StepArgs &sa, const float2 *tw, bool commit,
                                   hipStream_t s);
+
+// ---- the data-fidelity residual of the current state (residual.hip)
+// Scratch cap of a residual sweep: T of one launch's LEDs, [nl][B][nb][Np]
+// complex.  256 MB is the size of the chip's last-level cache, so what the row
+// kernel writes the column kernel can still find on the die, and at the metric
+// geometry (256 patches, r 33: 35 MB per LED) it holds 7 LEDs = 9 000 row and
+// 28 000 column blocks, tens of rounds of workgroups: a larger batch adds
+// memory and no parallelism.
+constexpr size_t kResidualScratchBytes = (size_t)256 << 20;
+// What a residual launch reads besides the state: the device copies of
+// order[] and the crop tables, and the context's residual scratch.
+struct ResArgs {
+    const int *order, *x0, *y0;
+    int i0;                    // position in order[] of the batch's first LED
+    float2 *T;                 // [nl][B][nb][Np] row-transform scratch
+    double *perr;              // [nl][B][nblk] one partial of E per column block
+    unsigned long long *pref;  //                and of S
+    double *err, *ref;         // [n_order][B] the folded sums
+    int nblk;
+};
+// Which kernel pair a context's sweep launches and how many LEDs at a time;
+// decided with the rest of the context (plan_context: no HIP call).
+struct ResidualPlan {
+    enum Kind { Reg256, Lds } kind;
+    FftPlan pl;                // of Np
+    StepKernel rows, cols;     // one LED's grid: the launch multiplies it by the batch
+    int nblk;                  // column blocks = partials per (LED, patch)
+    int nl;                    // LEDs per launch
+    size_t t_led;              // complex elements of T per LED
+};
+ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, int meas_g, bool fp16,
+                           const Switches &sw);
+hipError_t prepare_residual(const ResidualPlan &p);
+// rows, columns and fold of the nl LEDs at order[ra.i0 ...]
+hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, const ResArgs &ra, int nl,
+                                 const float2 *tw, hipStream_t s);
 
 // ---- batched transform of any length 2^a 3^b 5^c (fft_batch.hip)
 // Input band: sequences gs outside [qlo, qhi] and elements gi with

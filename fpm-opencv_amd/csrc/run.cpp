@@ -15,6 +15,16 @@ int fpm::refresh_objcrop(fpm_ctx *c) {
     return FPM_OK;
 }
 
+int fpm::refuse_capture(const fpm_ctx *c, const char *what) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(c->stream, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return set_err(FPM_ERR_INVAL, "%s on a capturing stream: %s is blocking and its %s cannot be "
+                       "replayed from a graph (fpm_hip.h)",
+                       what, what, c->split_ks > 1 ? "co-resident grids" : "launches");
+    return FPM_OK;
+}
+
 namespace {
 
 // ---- general path: patch groups ------------------------------------------------
@@ -88,17 +98,6 @@ hipError_t launch_general_iteration(fpm_ctx *c, bool use_graph, hipStream_t s) {
 }
 
 // ---- the steps of fpm_run ------------------------------------------------------
-// blocking (event waits, the abort-word read-back): never inside a capture
-int refuse_capture(const fpm_ctx *c) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(c->stream, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return set_err(FPM_ERR_INVAL, "fpm_run on a capturing stream: fpm_run is blocking and its %s cannot be "
-                       "replayed from a graph (fpm_hip.h)",
-                       c->split_ks > 1 ? "co-resident grids" : "launches");
-    return FPM_OK;
-}
-
 int grow_event_pool(fpm_ctx *c, size_t need) {
     while (c->evpool.size() < need) {
         hipEvent_t e;
@@ -224,7 +223,7 @@ int fpm_run(fpm_ctx *c, int iters) {
     c->clock = fpm_clock{};
     c->timing = fpm_timing{};
     HIP_TRY(hipSetDevice(c->device));
-    int rc = refuse_capture(c);
+    int rc = refuse_capture(c, "fpm_run");
     if (rc) return rc;
     if (c->clk) HIP_TRY(hipMemsetAsync(c->clk, 0, 3 * sizeof(unsigned long long), c->stream));
     // one event pair per iteration around the LED-update launches, one pair

@@ -27,6 +27,16 @@
 //                      (GY*Nlarge x GX*Nlarge complex64) is written as
 //                      objCrop_field.npy with pupils.npy [B][Np][Np] (SURVEY.md
 //                      8(f2)); result.json describes the grid
+//   --residual         report how well the state fits the data: fpm_residual
+//                      after fpm_init and after every iteration (the iterations
+//                      already run one fpm_run(ctx, 1) at a time, and a split run
+//                      ends bit for bit where a single one does), written to
+//                      result.json as "residual": per_iteration (itrCount + 1
+//                      values of sum E / sum S over all patches and LEDs),
+//                      per_patch_last, per_led_last (summed over patches, in
+//                      processing order) and sweep_ms; with --grid the patches
+//                      are the grid's; a figure whose S is 0 (all dark) is null.
+//                      The .npy outputs do not change
 //
 // Device selection: OPENCV_OPENCL_DEVICE (set by use_gpu.sh / use_cpu.sh) is
 // read with OpenCV's "<platform>:<type>:<device>" grammar and the scripts'
@@ -140,12 +150,14 @@ int main(int argc, char **argv) {
     }
     std::string out_dir = ".", led_table, path_opt = "auto";
     int device = 0, device_opt = -1, gx = 0, gy = 0;
+    bool want_residual = false;
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--out" && i + 1 < argc) out_dir = argv[++i];
         else if (a == "--device" && i + 1 < argc) device_opt = atoi(argv[++i]);
         else if (a == "--led-table" && i + 1 < argc) led_table = argv[++i];
         else if (a == "--path" && i + 1 < argc) path_opt = argv[++i];
+        else if (a == "--residual") want_residual = true;
         else if (a == "--grid" && i + 1 < argc) {
             if (sscanf(argv[++i], "%dx%d", &gx, &gy) != 2 || gx < 1 || gy < 1) {
                 std::cerr << "--grid wants GXxGY, e.g. 16x16" << std::endl;
@@ -291,10 +303,36 @@ int main(int argc, char **argv) {
         std::cerr << "fpm: " << fpm_last_error() << std::endl;
         return 1;
     }
+    // --residual: E and S [used][B] of the latest sweep, and their sums over
+    // everything after fpm_init and after each iteration
+    std::vector<double> res_e, res_s, res_iter_e, res_iter_s;
+    double res_ms = 0;
+    auto residual = [&]() {
+        res_e.resize((size_t)used * B);
+        res_s.resize((size_t)used * B);
+        if (fpm_residual(ctx, res_e.data(), res_s.data(), &res_ms)) return false;
+        double e = 0, s = 0;
+        for (size_t i = 0; i < res_e.size(); ++i) {
+            e += res_e[i];
+            s += res_s[i];
+        }
+        res_iter_e.push_back(e);
+        res_iter_s.push_back(s);
+        return true;
+    };
+    // sum E / sum S as JSON; null where every pixel summed is dark (S = 0)
+    auto put_ratio = [](FILE *f, const char *sep, double e, double s) {
+        if (s > 0) fprintf(f, "%s%.17g", sep, e / s);
+        else fprintf(f, "%snull", sep);
+    };
+    if (want_residual && !residual()) {
+        std::cerr << "fpm: " << fpm_last_error() << std::endl;
+        return 1;
+    }
     auto t_all = std::chrono::steady_clock::now();
     for (int itr = 1; itr <= itr_count; ++itr) {
         auto t0 = std::chrono::steady_clock::now();
-        if ((rc = fpm_run(ctx, 1))) {
+        if ((rc = fpm_run(ctx, 1)) || (want_residual && !residual())) {
             std::cerr << "fpm: " << fpm_last_error() << std::endl;
             return 1;
         }
@@ -345,6 +383,29 @@ int main(int argc, char **argv) {
                     info.path == FPM_PATH_FUSED ? "fused" : "general", dt);
             for (int i = 0; i < used; ++i) fprintf(f, "%s%d", i ? ", " : "", order[i]);
             fprintf(f, "],\n");
+            if (want_residual) {
+                fprintf(f, "  \"residual\": {\"per_iteration\": [");
+                for (size_t i = 0; i < res_iter_e.size(); ++i) put_ratio(f, i ? ", " : "", res_iter_e[i], res_iter_s[i]);
+                fprintf(f, "], \"per_patch_last\": [");
+                for (int b = 0; b < B; ++b) {
+                    double e = 0, s2 = 0;
+                    for (int i = 0; i < used; ++i) {
+                        e += res_e[(size_t)i * B + b];
+                        s2 += res_s[(size_t)i * B + b];
+                    }
+                    put_ratio(f, b ? ", " : "", e, s2);
+                }
+                fprintf(f, "], \"per_led_last\": [");
+                for (int i = 0; i < used; ++i) {
+                    double e = 0, s2 = 0;
+                    for (int b = 0; b < B; ++b) {
+                        e += res_e[(size_t)i * B + b];
+                        s2 += res_s[(size_t)i * B + b];
+                    }
+                    put_ratio(f, i ? ", " : "", e, s2);
+                }
+                fprintf(f, "], \"sweep_ms\": %.6f},\n", res_ms);
+            }
             if (grid) {
                 fprintf(f, "  \"grid\": {\"gx\": %d, \"gy\": %d, \"patches\": %d, \"frame\": [%d, %d], "
                            "\"patch_origin\": [%d, %d], \"patch_step\": %d},\n  \"bg_val\": [",

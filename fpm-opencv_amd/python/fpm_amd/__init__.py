@@ -49,11 +49,14 @@ HIP_SYMBOLS = (
     "fpm_download_objcrop_device", "fpm_set_stream", "fpm_get_info",
     "fpm_get_timing", "fpm_runFPM", "fpm_last_error", "fpm_version",
     "fpm_upload_frames", "fpm_download_stack", "fpm_get_info_sized", "fpm_abi_version",
-    "fpm_get_clock",
+    "fpm_get_clock", "fpm_residual",
 )
 # test-only entry points (include/fpm_hip_debug.h)
-HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall")
-ABI_VERSION = 5  # include/fpm_hip.h FPM_ABI_VERSION this mirror follows
+HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan")
+# fpm_debug_get_plan: general_kind / residual_kind values
+GENERAL_REG1024, GENERAL_REG256, GENERAL_LDS = 0, 1, 2
+RESIDUAL_REG256, RESIDUAL_LDS = 0, 1
+ABI_VERSION = 6  # include/fpm_hip.h FPM_ABI_VERSION this mirror follows
 
 
 class FpmError(RuntimeError):
@@ -130,8 +133,10 @@ def load_library(path: str = HIP_LIB):
         "fpm_get_info_sized": (C.c_int, [vp, C.POINTER(fpm_info), C.c_size_t]),
         "fpm_abi_version": (C.c_int, []),
         "fpm_debug_set_stall": (C.c_int, [vp, C.c_int]),
+        "fpm_debug_get_plan": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "fpm_get_timing": (C.c_int, [vp, C.POINTER(fpm_timing)]),
         "fpm_get_clock": (C.c_int, [vp, C.POINTER(fpm_clock)]),
+        "fpm_residual": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "fpm_runFPM": (C.c_int, [C.POINTER(fpm_problem), C.c_int, u16p, C.c_int,
                                  f32p, f32p, f32p, f32p]),
         "fpm_upload_frames": (C.c_int, [vp, C.POINTER(fpm_frames), vp, C.c_int, C.POINTER(C.c_int16)]),
@@ -287,6 +292,19 @@ class Solver:
     def synchronize(self):
         _check(_lib.fpm_synchronize(self._h))
 
+    def residual(self):
+        """Data-fidelity residual of the current state (fpm_residual; read-only,
+        blocking): err[i][b] = sum (|psi| - sqrt(I))^2 and ref[i][b] = sum I for
+        the LED at order[i] and patch b, float64 [n_order][n_patch], and the
+        sweep's event time ms."""
+        p = self.prob
+        err = np.empty((len(p.order), p.n_patch), np.float64)
+        ref = np.empty_like(err)
+        ms = C.c_double()
+        dp = C.POINTER(C.c_double)
+        _check(_lib.fpm_residual(self._h, err.ctypes.data_as(dp), ref.ctypes.data_as(dp), C.byref(ms)))
+        return dict(err=err, ref=ref, ms=ms.value)
+
     def download(self, objF=True, objCrop=True, pupil=True, support=True):
         p = self.prob
         B, L, N = p.n_patch, p.L, p.np_
@@ -311,6 +329,14 @@ class Solver:
         its split / distributed-mode handoffs; -1 switches it off."""
         _check(_lib.fpm_debug_set_stall(self._h, int(led)))
 
+    def debug_plan(self) -> dict:
+        """Test-only (include/fpm_hip_debug.h): the stack's device layout meas_g,
+        the general path's kind (GENERAL_*, -1 fused) and the residual sweep's
+        kernel pair (RESIDUAL_*)."""
+        g, k, r = C.c_int(), C.c_int(), C.c_int()
+        _check(_lib.fpm_debug_get_plan(self._h, C.byref(g), C.byref(k), C.byref(r)))
+        return dict(meas_g=g.value, general_kind=k.value, residual_kind=r.value)
+
     def timing(self) -> fpm_timing:
         t = fpm_timing()
         _check(_lib.fpm_get_timing(self._h, C.byref(t)))
@@ -322,6 +348,11 @@ class Solver:
         k = fpm_clock()
         _check(_lib.fpm_get_clock(self._h, C.byref(k)))
         return k
+
+
+def normalised_residual(d) -> np.ndarray:
+    """Per-patch normalised residual sum_i E / sum_i S of a Solver.residual() dict."""
+    return np.asarray(d["err"], np.float64).sum(0) / np.asarray(d["ref"], np.float64).sum(0)
 
 
 def run_fpm(prob: Problem, stack: np.ndarray, iters: int, device: int = 0):

@@ -34,8 +34,9 @@ extern "C" {
  * only the ABI-3 struct size (path .. fused_kernel) -- under ABI 4 it wrote
  * the whole struct, so a caller reading threads_per_wg from it must move to
  * fpm_get_info_sized; fpm_get_clock added; fpm_run refuses a capturing
- * stream.  fpm_abi_version() reports the library's revision. */
-#define FPM_ABI_VERSION   5
+ * stream.  (6): fpm_residual added.  fpm_abi_version() reports the library's
+ * revision. */
+#define FPM_ABI_VERSION   6
 
 #define FPM_OK            0
 #define FPM_ERR_INVAL   (-22)   /* bad argument / unsupported geometry      */
@@ -195,6 +196,21 @@ int  fpm_init(fpm_ctx *ctx);
  * a grid resident at once, which a replayed graph could not guarantee
  * beside other co-resident grids. */
 int  fpm_run(fpm_ctx *ctx, int iters);
+
+/* Data-fidelity residual of the current state (read-only: spectrum, pupil,
+ * maxima, objCrop and the stack are left bit for bit as they were).
+ *   err [n_order][n_patch]  E = sum_yx (|psi| - sqrt(I))^2, psi = ifft2(window * P)
+ *                           scaled 1/Np^2 like the reference's ifft2; no eps
+ *   ref [n_order][n_patch]  S = sum_yx I  (exact)
+ * Row i is order[i]'s LED.  Either pointer may be NULL, not both.
+ * elapsed_ms (may be NULL): event-to-event time of the sweep on the run stream.
+ * Blocking.  FPM_ERR_STATE before fpm_init; FPM_ERR_INVAL on a capturing
+ * stream, before anything is enqueued (as fpm_run).  fpm_timing and fpm_clock
+ * of the last fpm_run are not touched.  The first call allocates the sweep's
+ * scratch (at most 256 MB of row transforms unless one LED's exceed that;
+ * counted in fpm_info.device_bytes from then on).  Two calls on the same
+ * state return the same bits. */
+int  fpm_residual(fpm_ctx *ctx, double *err, double *ref, double *elapsed_ms);
 
 /* Wait for all work on the context stream. */
 int  fpm_synchronize(fpm_ctx *ctx);

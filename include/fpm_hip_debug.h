@@ -33,6 +33,13 @@ int fpm_debug_update_coef(const float *a, const float *c, const float *m, const 
  * FPM_ERR_DEVICE; -1 switches it off. */
 int fpm_debug_set_stall(fpm_ctx *ctx, int led);
 
+/* What plan_context decided and fpm_info does not report (any pointer may be
+ * NULL): meas_g = the stack's layout on the device (0 C-ABI, g > 0 the column
+ * layout with g-lane groups, Np transposed); general_kind = the general path's
+ * step kernels (0 Np 1024 register, 1 Np 256 register, 2 LDS; -1 on a fused
+ * context); residual_kind = fpm_residual's kernel pair (0 register, 1 LDS). */
+int fpm_debug_get_plan(const fpm_ctx *ctx, int *meas_g, int *general_kind, int *residual_kind);
+
 #ifdef __cplusplus
 }
 #endif
