@@ -125,7 +125,7 @@ __host__ __device__ inline int row_pitch(int np, int lc) {
     return p;
 }
 
-// ---- wave-private columns (general.hip k_colpass_wave, residual.hip k_res_cols_wave) ----
+// ---- wave-private columns (general.hip k_colpass_wave) ----
 constexpr int kWaveElems = 16;  // register elements per lane in a wave pass
 
 // one radix-R Stockham pass over the lane's column `cb` (lanes l, l + LPC,

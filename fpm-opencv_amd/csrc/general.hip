@@ -24,6 +24,16 @@
 // these a context runs depends on nothing but its sizes, so plan_general_step
 // decides it once and launch_general_step only launches.
 //
+// K1 and K2 (every generation) are templates over their argument struct:
+// StepArgs is the update step of one LED, ResArgs the residual sweep
+// (fpm_residual, residual.hip) over a batch of LEDs of order[], which is K1
+// and K2 up to the column IDFT with the residual sums as K2's tail.  The few
+// lines that differ stand under if constexpr or behind residual_dev.hpp's
+// overloads (res_led, res_T); the StepArgs instances are instruction for
+// instruction what the kernels were before they became templates
+// (tools/cmp_asm.py --pair).  plan_lds_ladder picks the generation and the
+// launch shapes for both.
+//
 // Pruning: P vanishes outside the support disk, so the inverse transform has
 // nonzero input only on the (2r+1)^2 box and only the box outputs of the
 // forward transform are ever used.  Row passes therefore run on nb = 2r+1 rows,
@@ -34,17 +44,21 @@
 #include "fft_lds.hpp"
 #include "fpm_state.hpp"
 #include "launch.hpp"
+#include "residual_dev.hpp"
 #include "update.hpp"
 
 namespace fpm {
 
 // ---- K1 ---------------------------------------------------------------------
-// grid (nb, B), block 256, LDS 2*Np float2
-__global__ void __launch_bounds__(256) k_gather_rowifft(DevState st, StepArgs sa, FftPlan pl,
+// grid (nb, B), block 256, LDS 2*Np float2.  Here and in K2, every generation:
+// A = ResArgs adds the grid's z, the LED of the sweep's batch.
+template <class A>
+__global__ void __launch_bounds__(256) k_gather_rowifft(DevState st, A a, FftPlan pl,
                                                         const float2 *__restrict__ tw) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     const int np = st.np, r = st.r, nb = st.nb;
-    const int row = blockIdx.x, b = blockIdx.y;
+    const int row = blockIdx.x, b = blockIdx.y, z = kIsRes<A> ? blockIdx.z : 0;
+    const StepArgs sa = res_led(a, z, np);
     const int ky = row - r;
     float2 *bufa = smem, *bufb = smem + np;
     const float2 *pup = st.pupil + (size_t)b * nb * nb;
@@ -56,36 +70,67 @@ __global__ void __launch_bounds__(256) k_gather_rowifft(DevState st, StepArgs sa
             const int kx = j - r;
             float2 o = spec_ld(st, b, (size_t)yrow * st.L + sa.xc + kx);
             float2 p = pup[row * nb + j];
-            bufa[(kx + np) % np] = cmul(o, p);
+            // (one index in two forms: each instance keeps the instructions it had,
+            // and the sweep's compare-and-add is 20 fewer than the %)
+            if constexpr (kIsRes<A>) bufa[kx < 0 ? kx + np : kx] = cmul(o, p);
+            else bufa[(kx + np) % np] = cmul(o, p);
         }
     }
     __syncthreads();
     float2 *res = stockham<true>(bufa, bufb, 1, pl, tw, threadIdx.x, blockDim.x);
-    float2 *T = st.T + ((size_t)b * nb + row) * np;
+    float2 *T = res_T(st, a, z, b, row, np);
     for (int i = threadIdx.x; i < np; i += blockDim.x) T[i] = res[i];
 }
 
 // ---- K2 ---------------------------------------------------------------------
 // grid (Np, B), block 256, LDS 2*Np float2. One column per block.
-__global__ void __launch_bounds__(256) k_colpass(DevState st, StepArgs sa, FftPlan pl,
+template <class A>
+__global__ void __launch_bounds__(256) k_colpass(DevState st, A a, FftPlan pl,
                                                  const float2 *__restrict__ tw) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     const int np = st.np, r = st.r, nb = st.nb;
-    const int x = blockIdx.x, b = blockIdx.y;
+    const int x = blockIdx.x, b = blockIdx.y, z = kIsRes<A> ? blockIdx.z : 0;
+    const StepArgs sa = res_led(a, z, np);
     float2 *bufa = smem, *bufb = smem + np;
-    float2 *T = st.T + (size_t)b * nb * np;
+    float2 *T = res_T(st, a, z, b, 0, np);
     for (int i = threadIdx.x; i < np; i += blockDim.x) bufa[i] = make_float2(0.f, 0.f);
     __syncthreads();
-    for (int j = threadIdx.x; j < nb; j += blockDim.x) bufa[(j - r + np) % np] = T[(size_t)j * np + x];
+    for (int j = threadIdx.x; j < nb; j += blockDim.x) {  // (the index as in K1)
+        if constexpr (kIsRes<A>) bufa[j - r < 0 ? j - r + np : j - r] = T[(size_t)j * np + x];
+        else bufa[(j - r + np) % np] = T[(size_t)j * np + x];
+    }
     __syncthreads();
     float2 *res = stockham<true>(bufa, bufb, 1, pl, tw, threadIdx.x, blockDim.x);
     float2 *oth = (res == bufa) ? bufb : bufa;
     const float inv_n2 = 1.0f / ((float)np * (float)np);
     const uint16_t *I = st.meas + ((size_t)sa.led * st.mB + b) * np * np;
-    for (int y = threadIdx.x; y < np; y += blockDim.x) res[y] = amp_replace(res[y], inv_n2, I[(size_t)y * np + x], st);
-    __syncthreads();
-    res = stockham<false>(res, oth, 1, pl, tw, threadIdx.x, blockDim.x);
-    for (int j = threadIdx.x; j < nb; j += blockDim.x) T[(size_t)j * np + x] = res[(j - r + np) % np];
+    if constexpr (kIsRes<A>) {
+        const int g = st.meas_g;
+        float acc = 0.f;
+        unsigned isum = 0;
+        if (g) {  // uniform: the stored column x is contiguous, position p holds row (p mod (Np/g)) g + p / (Np/g)
+            const int npg = np / g;
+            const float rnpg = 1.0f / (float)npg;
+            for (int p = threadIdx.x; p < np; p += blockDim.x) {
+                const int t = udiv(p, npg, rnpg), m = p - t * npg;
+                const unsigned iv = I[(size_t)x * np + p];
+                acc = res_add(acc, res[m * g + t], inv_n2, iv);
+                isum += iv;
+            }
+        } else {
+            for (int y = threadIdx.x; y < np; y += blockDim.x) {
+                const unsigned iv = I[(size_t)y * np + x];
+                acc = res_add(acc, res[y], inv_n2, iv);
+                isum += iv;
+            }
+        }
+        res_block_partial<4>(acc, isum, a, ((size_t)z * st.B + b) * a.nblk + x);
+    } else {
+        for (int y = threadIdx.x; y < np; y += blockDim.x) res[y] = amp_replace(res[y], inv_n2, I[(size_t)y * np + x], st);
+        __syncthreads();
+        res = stockham<false>(res, oth, 1, pl, tw, threadIdx.x, blockDim.x);
+        for (int j = threadIdx.x; j < nb; j += blockDim.x) T[(size_t)j * np + x] = res[(j - r + np) % np];
+    }
 }
 
 // ---- K3 ---------------------------------------------------------------------
@@ -254,12 +299,13 @@ int pupil_parts(int nb) { return std::max(1, (nb * nb + kCommitPx - 1) / kCommit
 // the twiddles beside it: the row transforms of a block run together, in
 // place, instead of one 256-thread block per row with global twiddle reads.
 // grid (ceil(nb / C), B), block NT.
-template <int NT, int E>
-__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16 ? 4 : 1))) k_gather_rowifft_tiled(DevState st, StepArgs sa, FftPlan pl,
+template <int NT, int E, class A>
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16 ? 4 : 1))) k_gather_rowifft_tiled(DevState st, A a, FftPlan pl,
                                                              const float2 *__restrict__ tw, int lc) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     const int np = st.np, r = st.r, nb = st.nb, C = 1 << lc, lss = row_pitch(np, lc);
-    const int j0 = blockIdx.x << lc, b = blockIdx.y;
+    const int j0 = blockIdx.x << lc, b = blockIdx.y, z = kIsRes<A> ? blockIdx.z : 0;
+    const StepArgs sa = res_led(a, z, np);
     const int cs = min(C, nb - j0);
     float2 *tile = smem, *stw = smem + (size_t)C * lss;
     const float2 *pup = st.pupil + (size_t)b * nb * nb;
@@ -276,7 +322,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
     }
     __syncthreads();
     tile_transform_ex<true, NT, E>(tile, pl, lc, lss, 1, stw);                              // :365
-    float2 *T = st.T + ((size_t)b * nb + j0) * np;
+    float2 *T = res_T(st, a, z, b, j0, np);
     const float rnp = 1.0f / (float)np;
     for (int idx = threadIdx.x; idx < cs * np; idx += NT) {
         const int c = udiv(idx, np, rnp), i = idx - c * np;
@@ -330,16 +376,17 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
 // C: its missing columns are zero and never stored).  grid (ceil(Np / C), B),
 // block NT (256 when the tile fits its register-lifted passes, so a 16 x 200
 // tile keeps every wave busy instead of idling half of a 512-thread block).
-template <int NT, int E>
-__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16 ? 4 : 1))) k_colpass_tiled(DevState st, StepArgs sa, FftPlan pl,
+template <int NT, int E, class A>
+__global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16 ? 4 : 1))) k_colpass_tiled(DevState st, A a, FftPlan pl,
                                                       const float2 *__restrict__ tw, int lc) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     const int np = st.np, r = st.r, nb = st.nb, C = 1 << lc, cm = C - 1;
-    const int x0 = blockIdx.x << lc, b = blockIdx.y;
+    const int x0 = blockIdx.x << lc, b = blockIdx.y, z = kIsRes<A> ? blockIdx.z : 0;
+    const StepArgs sa = res_led(a, z, np);
     const int cs = min(C, np - x0);            // columns present in this tile
     float2 *tile = smem;                       // np * C
     float2 *stw = smem + (size_t)np * C;       // np twiddles
-    float2 *T = st.T + (size_t)b * nb * np;
+    float2 *T = res_T(st, a, z, b, 0, np);
     for (int i = threadIdx.x; i < np; i += NT) stw[i] = tw[i];
     for (int i = threadIdx.x; i < np * C; i += NT) tile[i] = make_float2(0.f, 0.f);
     __syncthreads();
@@ -352,17 +399,41 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
     tile_transform<true, NT, E>(tile, pl, lc, stw);
     const float inv_n2 = 1.0f / ((float)np * (float)np);
     const uint16_t *I = st.meas + ((size_t)sa.led * st.mB + b) * np * np;
-    for (int idx = threadIdx.x; idx < np * C; idx += NT) {
-        const int y = idx >> lc, c = idx & cm;
-        if (c >= cs) continue;
-        tile[idx] = amp_replace(tile[idx], inv_n2, I[(size_t)y * np + x0 + c], st);
-    }
-    __syncthreads();
-    tile_transform<false, NT, E>(tile, pl, lc, stw);
-    for (int idx = threadIdx.x; idx < nb * C; idx += NT) {
-        const int j = idx >> lc, c = idx & cm;
-        const int i = j - r < 0 ? j - r + np : j - r;
-        if (c < cs) T[(size_t)j * np + x0 + c] = tile[i * C + c];
+    if constexpr (kIsRes<A>) {
+        // rows in natural order, the tile's C columns across adjacent lanes (no
+        // LDS bank conflict).  The stack is read as C*2-byte row segments in
+        // the C-ABI layout; in a column layout row y of column x lies at
+        // x Np + (y mod g)(Np / g) + y / g, so the block still reads each of its
+        // columns' 2 Np bytes exactly once.  (Walking a stored column in memory
+        // order instead would put a wave's 64 LDS reads 2^lc g rows apart, all in
+        // one bank.)
+        const int g = st.meas_g;
+        float acc = 0.f;
+        unsigned isum = 0;
+        const int npg = g ? np / g : 1;
+        const float rg = 1.0f / (float)(g ? g : 1);
+        for (int idx = threadIdx.x; idx < np * C; idx += NT) {
+            const int y = idx >> lc, c = idx & cm;
+            if (c >= cs) continue;
+            const int m = udiv(y, g ? g : 1, rg), t = y - m * g;  // g > 0: y = t + g m
+            const unsigned iv = g ? I[(size_t)(x0 + c) * np + t * npg + m] : I[(size_t)y * np + x0 + c];
+            acc = res_add(acc, tile[idx], inv_n2, iv);
+            isum += iv;
+        }
+        res_block_partial<NT / 64>(acc, isum, a, ((size_t)z * st.B + b) * a.nblk + blockIdx.x);
+    } else {
+        for (int idx = threadIdx.x; idx < np * C; idx += NT) {
+            const int y = idx >> lc, c = idx & cm;
+            if (c >= cs) continue;
+            tile[idx] = amp_replace(tile[idx], inv_n2, I[(size_t)y * np + x0 + c], st);
+        }
+        __syncthreads();
+        tile_transform<false, NT, E>(tile, pl, lc, stw);
+        for (int idx = threadIdx.x; idx < nb * C; idx += NT) {
+            const int j = idx >> lc, c = idx & cm;
+            const int i = j - r < 0 ? j - r + np : j - r;
+            if (c < cs) T[(size_t)j * np + x0 + c] = tile[i * C + c];
+        }
     }
 }
 
@@ -378,13 +449,14 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
 // (rows lane + 64q of its wave's columns) are loaded into registers before
 // the inverse transform, so their latency hides behind it.
 // grid (ceil(Np / (NW*CW)), B), block 64*NW, LDS (NW*CW*pitch + Np) float2
-template <int NW, int CW>
+template <int NW, int CW, class A>
 __global__ void __launch_bounds__(64 * NW)
-k_colpass_wave(DevState st, StepArgs sa, FftPlan pl, const float2 *__restrict__ tw, int P) {
+k_colpass_wave(DevState st, A a, FftPlan pl, const float2 *__restrict__ tw, int P) {
     constexpr int NT = 64 * NW, C = NW * CW, NQY = 16 / CW;
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     const int np = st.np, r = st.r, nb = st.nb;
-    const int x0 = blockIdx.x * C, b = blockIdx.y;
+    const int x0 = blockIdx.x * C, b = blockIdx.y, z = kIsRes<A> ? blockIdx.z : 0;
+    const StepArgs sa = res_led(a, z, np);
     const int cs = min(C, np - x0);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     constexpr int LPC = 64 / CW;
@@ -392,17 +464,36 @@ k_colpass_wave(DevState st, StepArgs sa, FftPlan pl, const float2 *__restrict__ 
     float2 *wb = smem + (size_t)w * CW * P;
     float2 *cb = wb + (lane / LPC) * P;  // this lane's column in the radix passes
     const int l = lane % LPC;
-    float2 *T = st.T + (size_t)b * nb * np;
+    float2 *T = res_T(st, a, z, b, 0, np);
     // this lane's measurement values: rows lane + 64q of the wave's columns
     const uint16_t *I = st.meas + ((size_t)sa.led * st.mB + b) * np * np;
-    uint16_t iv[NQY * CW];
+    typename std::conditional<kIsRes<A>, unsigned, uint16_t>::type iv[NQY * CW];
+    if constexpr (kIsRes<A>) {
+        // the sweep reads the stack where it lies: every load issued before the
+        // first use (clamped in-bounds, masked afterwards); in a column layout
+        // row y of column x lies at x Np + (y mod g)(Np / g) + y / g
+        const int g = st.meas_g;
+        const int npg = g ? np / g : 1;
+        const float rg = 1.0f / (float)(g ? g : 1);
 #pragma unroll
-    for (int q = 0; q < NQY; ++q) {
-        const int y = lane + 64 * q;
+        for (int q = 0; q < NQY; ++q) {
+            const int y = min(lane + 64 * q, np - 1);
+            const int m = udiv(y, g ? g : 1, rg), t = y - m * g;  // g > 0: y = t + g m
 #pragma unroll
-        for (int c = 0; c < CW; ++c) {
-            const int x = w * CW + c;
-            iv[q * CW + c] = (y < np && x < cs) ? I[(size_t)y * np + x0 + x] : (uint16_t)0;
+            for (int c = 0; c < CW; ++c) {
+                const int x = x0 + min(w * CW + c, cs - 1);
+                iv[q * CW + c] = g ? I[(size_t)x * np + t * npg + m] : I[(size_t)y * np + x];
+            }
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < NQY; ++q) {
+            const int y = lane + 64 * q;
+#pragma unroll
+            for (int c = 0; c < CW; ++c) {
+                const int x = w * CW + c;
+                iv[q * CW + c] = (y < np && x < cs) ? I[(size_t)y * np + x0 + x] : (uint16_t)0;
+            }
         }
     }
     for (int i = threadIdx.x; i < np; i += NT) stw[i] = tw[i];
@@ -418,27 +509,113 @@ k_colpass_wave(DevState st, StepArgs sa, FftPlan pl, const float2 *__restrict__ 
     __syncthreads();
     wave_transform<true, LPC>(cb, pl, stw, l);
     const float inv_n2 = 1.0f / ((float)np * (float)np);
+    if constexpr (kIsRes<A>) {
+        float acc = 0.f;
+        unsigned isum = 0;
 #pragma unroll
-    for (int q = 0; q < NQY; ++q) {
-        const int y = lane + 64 * q;
-        if (y >= np) continue;
+        for (int q = 0; q < NQY; ++q) {
+            const int y = lane + 64 * q;
 #pragma unroll
-        for (int c = 0; c < CW; ++c) {
-            float2 *e = wb + c * P + y;
-            *e = amp_replace(*e, inv_n2, iv[q * CW + c], st);
+            for (int c = 0; c < CW; ++c) {
+                if (y >= np || w * CW + c >= cs) continue;
+                acc = res_add(acc, wb[c * P + y], inv_n2, iv[q * CW + c]);
+                isum += iv[q * CW + c];
+            }
         }
-    }
-    wave_sync();
-    wave_transform<false, LPC>(cb, pl, stw, l);
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < nb * C; idx += NT) {
-        const int j = udiv(idx, C, rC), c = idx - j * C;
-        const int i = j - r < 0 ? j - r + np : j - r;
-        if (c < cs) T[(size_t)j * np + x0 + c] = smem[c * P + i];
+        res_block_partial<NW>(acc, isum, a, ((size_t)z * st.B + b) * a.nblk + blockIdx.x);
+    } else {
+#pragma unroll
+        for (int q = 0; q < NQY; ++q) {
+            const int y = lane + 64 * q;
+            if (y >= np) continue;
+#pragma unroll
+            for (int c = 0; c < CW; ++c) {
+                float2 *e = wb + c * P + y;
+                *e = amp_replace(*e, inv_n2, iv[q * CW + c], st);
+            }
+        }
+        wave_sync();
+        wave_transform<false, LPC>(cb, pl, stw, l);
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < nb * C; idx += NT) {
+            const int j = udiv(idx, C, rC), c = idx - j * C;
+            const int i = j - r < 0 ? j - r + np : j - r;
+            if (c < cs) T[(size_t)j * np + x0 + c] = smem[c * P + i];
+        }
     }
 }
 
 // ---- the plan and the step launcher -------------------------------------------
+// Which generation of K1 / K3 and of K2 a size runs, with the launch shapes:
+// decided here for the update step and for the residual sweep alike.
+// step: the update step, which trades tile size for block count when a few
+// large patches would leave the chip short of blocks (the sweep gets its
+// blocks from the batch, and alone honours FPM_RES_ONE_SEQ).
+LdsLadder plan_lds_ladder(const FftPlan &pl, int np, int nb, int B, const Switches &sw, bool step) {
+    LdsLadder l{};
+    const bool one_seq = !step && sw.res_one_seq;  // the fallback of sizes where not even two fit, at any size
+    const size_t lds = 2 * (size_t)np * sizeof(float2);  // of the one-sequence kernels
+    // row kernels: up to 16 box rows per block (one row per block when not
+    // even 2 rows fit a 256-thread tile)
+    int lr = one_seq ? 0 : 4;
+    while (lr > 0 && !fft_fits(pl, lr, 256)) --lr;
+    auto rblk = [&](int k) { return ((nb + (1 << k) - 1) >> k) * B; };
+    while (step && lr > 1 && rblk(lr) < 512) --lr;
+    if (lr > 0) {
+        // 16 register elements per thread when the tile allows (fewer VGPRs, more
+        // waves per SIMD to hide the LDS round trips of each pass), else 24
+        l.row_e = fft_fits(pl, lr, 256, 16) ? 16 : 24;
+        l.rows = StepKernel{nullptr, dim3((nb + (1 << lr) - 1) >> lr, B), dim3(256),
+                            ((size_t)row_pitch(np, lr) * (1 << lr) + np) * sizeof(float2), lr};
+    } else {
+        l.rows = StepKernel{nullptr, dim3(nb, B), dim3(256), lds, 0};
+    }
+    // tiled column pass: up to 16 columns per block while the tile fits the
+    // in-place register-lifted transform (the step: down to 4 for blocks);
+    // one column per block when not even 2 columns fit
+    int lc = one_seq ? 0 : 4;
+    while (lc > 0 && !fft_fits(pl, lc)) --lc;
+    auto cblk = [&](int k) { return ((np + (1 << k) - 1) >> k) * B; };
+    while (step && lc > 2 && cblk(lc) < 512) --lc;
+    const int cw = colw_cw(pl);
+    if (cw > 1 && !sw.no_wave_cols && !one_seq) {
+        // wave-private columns where a wave holds at least two (Np <= 512):
+        // 4 waves x CW columns; FPM_NO_WAVE_COLS=1: tiled
+        const int P = colw_pitch(np), C = 4 * cw;
+        l.cw = cw;
+        l.cols = StepKernel{nullptr, dim3((np + C - 1) / C, B), dim3(256), ((size_t)C * P + np) * sizeof(float2), P};
+    } else if (lc > 0) {
+        // 256 threads when the tile fits their register-lifted passes, else 512
+        const int nt = fft_fits(pl, lc, 256) ? 256 : kFftThreads;
+        l.col_e = fft_fits(pl, lc, nt, 16) ? 16 : 24;
+        l.cols = StepKernel{nullptr, dim3((np + (1 << lc) - 1) >> lc, B), dim3(nt),
+                            ((size_t)np * (1 << lc) + np) * sizeof(float2), lc};
+    } else {
+        l.cols = StepKernel{nullptr, dim3(np, B), dim3(256), lds, 0};
+    }
+    return l;
+}
+
+// the ladder's K1 / K2 for the update step (A = StepArgs) or the sweep (ResArgs)
+template <class A>
+static void pick_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols) {
+    rows = l.rows;
+    rows.fn = l.row_e == 16 ? (const void *)k_gather_rowifft_tiled<256, 16, A>
+              : l.row_e     ? (const void *)k_gather_rowifft_tiled<256, 24, A>
+                            : (const void *)k_gather_rowifft<A>;
+    cols = l.cols;
+    const bool e16 = l.col_e == 16;
+    if (l.cw)
+        cols.fn = l.cw == 4 ? (const void *)k_colpass_wave<4, 4, A> : (const void *)k_colpass_wave<4, 2, A>;
+    else if (!l.col_e)
+        cols.fn = (const void *)k_colpass<A>;
+    else if (cols.block.x == 256)
+        cols.fn = e16 ? (const void *)k_colpass_tiled<256, 16, A> : (const void *)k_colpass_tiled<256, 24, A>;
+    else
+        cols.fn = e16 ? (const void *)k_colpass_tiled<kFftThreads, 16, A>
+                      : (const void *)k_colpass_tiled<kFftThreads, 24, A>;
+}
+
 GeneralPlan plan_general_step(const DevState &st, GeneralPlan::Kind kind, const FftPlan &pl, const Switches &sw) {
     GeneralPlan p{};
     p.pl = pl;
@@ -447,70 +624,17 @@ GeneralPlan plan_general_step(const DevState &st, GeneralPlan::Kind kind, const 
     // the context's plan decides which (plan_context, create.cpp)
     p.kind = kind;
     if (p.kind != GeneralPlan::Lds) return p;
-    const int np = st.np;
-    const size_t lds = 2 * (size_t)np * sizeof(float2);  // of the one-sequence kernels
-    // row kernels: up to 16 box rows per block, fewer while a few large
-    // patches would leave the chip short of blocks (one row per block when
-    // not even 2 rows fit a 256-thread tile)
-    int lr = 4;
-    while (lr > 0 && !fft_fits(pl, lr, 256)) --lr;
-    auto rblk = [&](int l) { return ((st.nb + (1 << l) - 1) >> l) * st.B; };
-    while (lr > 1 && rblk(lr) < 512) --lr;
-    if (lr > 0) {
-        // 16 register elements per thread when the tile allows (fewer VGPRs, more
-        // waves per SIMD to hide the LDS round trips of each pass), else 24
-        const bool r16 = fft_fits(pl, lr, 256, 16);
-        const size_t ldr = ((size_t)row_pitch(np, lr) * (1 << lr) + np) * sizeof(float2);
-        p.k1 = p.k3 = StepKernel{nullptr, dim3((st.nb + (1 << lr) - 1) >> lr, st.B), dim3(256), ldr, lr};
-        p.k1.fn = r16 ? (const void *)k_gather_rowifft_tiled<256, 16> : (const void *)k_gather_rowifft_tiled<256, 24>;
-        p.k3.fn = r16 ? (const void *)k_rowfft_update_tiled<256, 16> : (const void *)k_rowfft_update_tiled<256, 24>;
-    } else {
-        p.k1 = p.k3 = StepKernel{nullptr, dim3(st.nb, st.B), dim3(256), lds, 0};
-        p.k1.fn = (const void *)k_gather_rowifft;
-        p.k3.fn = (const void *)k_rowfft_update;
-    }
-    // tiled column pass: up to 16 columns per block while the tile fits the
-    // in-place register-lifted transform, fewer (down to 4) when a few large
-    // patches would leave the chip short of blocks; one column per block when
-    // not even 2 columns fit
-    int lc = 4;
-    while (lc > 0 && !fft_fits(pl, lc)) --lc;
-    auto nblk = [&](int l) { return ((np + (1 << l) - 1) >> l) * st.B; };
-    while (lc > 2 && nblk(lc) < 512) --lc;
-    const int cw = colw_cw(pl);
-    if (cw > 1 && !sw.no_wave_cols) {
-        // wave-private columns: 4 waves x CW columns, 8 waves when a wave
-        // holds a single (long) column
-        const int P = colw_pitch(np);
-        const int nw = cw == 1 ? 8 : 4, C = nw * cw;
-        p.k2 = StepKernel{nullptr, dim3((np + C - 1) / C, st.B), dim3(64 * nw),
-                          ((size_t)C * P + np) * sizeof(float2), P};
-        if (cw == 4) p.k2.fn = (const void *)k_colpass_wave<4, 4>;
-        else if (cw == 2) p.k2.fn = (const void *)k_colpass_wave<4, 2>;
-        else p.k2.fn = (const void *)k_colpass_wave<8, 1>;
-    } else if (lc > 0) {
-        p.k2 = StepKernel{nullptr, dim3((np + (1 << lc) - 1) >> lc, st.B), dim3(256),
-                          ((size_t)np * (1 << lc) + np) * sizeof(float2), lc};
-        if (fft_fits(pl, lc, 256, 16)) {
-            p.k2.fn = (const void *)k_colpass_tiled<256, 16>;
-        } else if (fft_fits(pl, lc, 256)) {
-            p.k2.fn = (const void *)k_colpass_tiled<256, 24>;
-        } else {
-            p.k2.block = dim3(kFftThreads);
-            p.k2.fn = fft_fits(pl, lc, kFftThreads, 16) ? (const void *)k_colpass_tiled<kFftThreads, 16>
-                                                        : (const void *)k_colpass_tiled<kFftThreads, 24>;
-        }
-    } else {
-        p.k2 = StepKernel{(const void *)k_colpass, dim3(np, st.B), dim3(256), lds, 0};
-    }
+    const LdsLadder l = plan_lds_ladder(pl, st.np, st.nb, st.B, sw, true);
+    pick_lds_kernels<StepArgs>(l, p.k1, p.k2);
+    p.k3 = l.rows;
+    p.k3.fn = l.row_e == 16 ? (const void *)k_rowfft_update_tiled<256, 16>
+              : l.row_e     ? (const void *)k_rowfft_update_tiled<256, 24>
+                            : (const void *)k_rowfft_update;
     return p;
 }
 
-static void launch_step_kernel(const StepKernel &k, DevState st, StepArgs sa, FftPlan pl, const float2 *tw,
-                               hipStream_t s) {
-    int arg = k.arg;
-    void *args[] = {&st, &sa, &pl, &tw, &arg};  // the one-sequence kernels take the first four
-    (void)hipLaunchKernel(k.fn, k.grid, k.block, args, k.lds, s);
+void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols) {
+    pick_lds_kernels<ResArgs>(l, rows, cols);
 }
 
 hipError_t launch_general_step(const GeneralPlan &plan, const DevState &st, int led, int x0, int y0,
@@ -525,9 +649,9 @@ hipError_t launch_general_step(const GeneralPlan &plan, const DevState &st, int 
     } else if (plan.kind == GeneralPlan::Reg256) {
         return launch_np256_rows_cols(st, sa, tw, !first, s);  // K4 inside, K5 folded
     } else {
-        launch_step_kernel(plan.k1, st, sa, plan.pl, tw, s);
-        launch_step_kernel(plan.k2, st, sa, plan.pl, tw, s);
-        launch_step_kernel(plan.k3, st, sa, plan.pl, tw, s);
+        (void)launch_step_kernel(plan.k1, st, sa, plan.pl, tw, s);
+        (void)launch_step_kernel(plan.k2, st, sa, plan.pl, tw, s);
+        (void)launch_step_kernel(plan.k3, st, sa, plan.pl, tw, s);
     }
     // K4's block size follows the LED's ROI tile columns
     const int nrow = (sa.yc + st.r) / kTile - (sa.yc - st.r) / kTile + 1;

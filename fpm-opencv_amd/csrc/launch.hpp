@@ -34,6 +34,24 @@ struct StepKernel {
     size_t lds;  // dynamic LDS bytes
     int arg;     // rows per block lr, columns per block lc (both log2) or the column pitch P
 };
+// One launch of an LDS step kernel for the update step (A = StepArgs) or for
+// nl LEDs of the residual sweep (ResArgs: blockIdx.z is the LED of the batch)
+template <class A>
+inline hipError_t launch_step_kernel(const StepKernel &k, DevState st, A a, FftPlan pl, const float2 *tw,
+                                     hipStream_t s, int nl = 1) {
+    int arg = k.arg;
+    void *args[] = {&st, &a, &pl, &tw, &arg};  // the one-sequence kernels take the first four
+    return hipLaunchKernel(k.fn, dim3(k.grid.x, k.grid.y, nl), k.block, args, k.lds, s);
+}
+// Which generation of the LDS row (K1 / K3) and column (K2) kernels a size
+// runs, and their launch shapes (plan_lds_ladder, general.hip)
+struct LdsLadder {
+    StepKernel rows, cols;  // fn unset
+    int row_e;              // tiled rows: register elements per thread (16 / 24); 0: one row per block
+    int cw;                 // wave-private columns per wave (4 / 2); 0: tiled, or one column per block
+    int col_e;              // tiled columns: register elements per thread (16 / 24); 0 otherwise
+};
+LdsLadder plan_lds_ladder(const FftPlan &pl, int np, int nb, int B, const Switches &sw, bool step);
 // What launch_general_step launches for a context (a patch group): nothing in
 // it depends on the LED, so fpm_create makes it once (plan_general_step).
 struct GeneralPlan {
@@ -92,6 +110,10 @@ struct ResidualPlan {
 };
 ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, int meas_g, bool fp16,
                            const Switches &sw);
+// the sweep's kernels are the step's, instantiated for ResArgs: the ladder's
+// K1 / K2 (general.hip) and the Np 256 register column kernel (np256.hip)
+void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols);
+const void *residual_cols256_kernel();
 hipError_t prepare_residual(const ResidualPlan &p);
 // rows, columns and fold of the nl LEDs at order[ra.i0 ...]
 hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, const ResArgs &ra, int nl,

@@ -15,7 +15,10 @@
 //                      amplitude replacement against the stack in the fused
 //                      column layout (meas_layout g = 16: lane t holds rows
 //                      t + 16 m of its column, 32 contiguous bytes), column
-//                      DFT, box rows back to T
+//                      DFT, box rows back to T.  A template over the
+//                      argument struct: for ResArgs it is the residual sweep's
+//                      column kernel (residual.hip), the same up to the column
+//                      IDFT for a batch of LEDs, then the residual sums
 //   R2 k_rows256_fwd   a block per 16-row tile row of the spectrum, a group
 //                      per box row: T row in, row DFT, object update and pupil
 //                      numerator on the row's disk pixels, then the tile
@@ -32,30 +35,20 @@
 // Blocks are mapped so that every kernel's blocks of patch b land on XCD
 // b mod 8 (round-robin dispatch; only a placement, correctness does not
 // depend on it): a patch's T (nb x 256 x 8 B = 346 KB at r 84), window and
-// pupil are written and read back on one XCD.
+// pupil are written and read back on one XCD.  The block shape, the index
+// helpers and the launch sizes are np256_layout.hpp's.
 #include <hip/hip_runtime.h>
 
 #include "cpk.hpp"
 #include "dftL.hpp"
 #include "fpm_state.hpp"
 #include "launch.hpp"
-
-#include <algorithm>
+#include "np256_layout.hpp"
+#include "residual_dev.hpp"
 
 namespace fpm {
 
-namespace n256 {
-constexpr int N = 256, H = N / 2;
-constexpr int WPB = 4;            // waves per block
-constexpr int NT = 64 * WPB;
-constexpr int GPB = 4 * WPB;      // 16-lane groups per block: rows (R1, R2) or columns (C) per block
-constexpr int SP = GPB + 1;       // strip row pitch (complex)
-static_assert(NT == N, "one twiddle per thread");
-}  // namespace n256
-
 namespace {
-
-__device__ __forceinline__ int fold256(int k) { return k < n256::H ? k : k - n256::N; }  // signed frequency
 
 // max over each row of 16 lanes (one group) of values >= +0, in every lane of
 // the row (the DPP steps of wave_max_nonneg without the cross-row fold)
@@ -66,20 +59,6 @@ __device__ __forceinline__ float row16_max_nonneg(float x) {
     v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, false));  // row_half_mirror
     v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, false));  // row_mirror
     return __uint_as_float(v);
-}
-
-// block -> (patch b, sub-block) of a 1-D grid of nsub * xcd_patches(B)
-// blocks, patch b on XCD b mod 8; false for the padding blocks of patches
-// b >= B (B not a multiple of 8), which exit at once.  Against the plain
-// b = block / nsub: 1.20-1.22 -> 1.22-1.24 M at dataset_mono Np 256, 64
-// patches (profiles/r06_ab/np256_register_path_ab.txt)
-__host__ __device__ __forceinline__ int xcd_patches(int B) { return (B + 7) & ~7; }
-__device__ __forceinline__ bool xcd_block(int nsub, int B, int &b, int &sub) {
-    const int id = blockIdx.x;
-    const int k = id >> 3, q = k / nsub;
-    b = (id & 7) + 8 * q;
-    sub = k - q * nsub;
-    return b < B;
 }
 
 // R1: grid (ceil(nb / GPB) * xcd_patches(B)), block NT, LDS (N + GPB XTILE_H) complex
@@ -169,19 +148,25 @@ __global__ void __launch_bounds__(n256::NT) k_rows256_inv(DevState st, StepArgs 
 }
 
 // C: grid ((N / GPB) * xcd_patches(B)), block NT, LDS (N + max(nb SP, GPB XTILE_H)) complex
-__global__ void __launch_bounds__(n256::NT) k_cols256(DevState st, StepArgs sa, const float2 *__restrict__ tw) {
+template <class A>
+__global__ void __launch_bounds__(n256::NT) k_cols256(DevState st, A a, const float2 *__restrict__ tw) {
     using namespace n256;
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     const int g = threadIdx.x >> 4, t = threadIdx.x & 15, xrd = exch_rbase_half(t);
     const int r = st.r, nb = st.nb;
-    int b, sub;
-    if (!xcd_block(N / GPB, st.B, b, sub)) return;  // block-uniform
+    int z = 0, b, sub;
+    if constexpr (kIsRes<A>) {
+        if (!res_xcd_block(N / GPB, st.B, z, b, sub)) return;  // block-uniform
+    } else {
+        if (!xcd_block(N / GPB, st.B, b, sub)) return;  // block-uniform
+    }
+    const StepArgs sa = res_led(a, z, N);
     const int x0 = sub * GPB;
     const float2 twv = tw[threadIdx.x];
     float2 *twL = sm;
     float2 *strip = sm + N;              // nb x SP (box rows only); the group tiles
     float2 *wt = strip + g * XTILE_H;    // alias it while every column is in registers
-    float2 *T = st.T + (size_t)b * nb * N + x0;
+    float2 *T = res_T(st, a, z, b, 0, N) + x0;
     // this group's measurement column, rows t + 16 m (meas_layout g = 16:
     // stored[x Np + 16 t + m] = I[t + 16 m][x]), two 16-byte loads per lane
     const uint4 *Ic = (const uint4 *)(st.meas + (((size_t)sa.led * st.mB + b) * N + x0 + g) * N + 16 * t);
@@ -203,40 +188,51 @@ __global__ void __launch_bounds__(n256::NT) k_cols256(DevState st, StepArgs sa, 
         if (NT * k < tot && idx < tot) strip[(idx / GPB) * SP + (idx % GPB)] = tv[k];
     }
     __syncthreads();
-    // FFT row i of a column is box row i + r (i <= r) or i - N + r (i >= N - r);
-    // every other row is zero (:364)
-    auto boxrow = [&](int i) { return i <= r ? i + r : (i >= N - r ? i - N + r : -1); };
+    // the column's FFT rows from the box rows, zero elsewhere (:364)
     float2 v[16];
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
-        const int j = boxrow(t + 16 * m);
+        const int j = boxrow(t + 16 * m, r);
         v[m] = j >= 0 ? strip[j * SP + g] : make_float2(0.f, 0.f);
     }
     __syncthreads();  // the strip is the groups' exchange space from here
     float2 y[16];
     dft256_full<true, true>(v, y, wt, LdsTw{twL, t, 1}, t, xrd);  // :365 (columns); y[m] = row t + 16 m
-    // amplitude replacement (:378-394), np1024.hip's form: with y the unscaled
-    // IDFT value, psi = y / N^2 and sqrt(I) psi / |psi + eps (1 + i)| =
-    // y sqrt(I) / |y + eps N^2 (1 + i)|
-    const float nn = (float)N * (float)N, epsn = st.eps * nn, epsn_im = st.eps_im * nn;
     const unsigned iw[8] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w};
+    if constexpr (kIsRes<A>) {
+        const float inv_n2 = 1.0f / ((float)N * (float)N);
+        float acc = 0.f;
+        unsigned isum = 0;
 #pragma unroll
-    for (int m = 0; m < 16; ++m) {
-        const float iv = (float)((iw[m >> 1] >> (16 * (m & 1))) & 0xffffu);
-        const float2 u = y[m];
-        const float tr = u.x + epsn, ti = u.y + epsn_im;
-        const float s = amp_scale(__builtin_fmaf(tr, tr, ti * ti), iv);
-        y[m] = make_float2(u.x * s, u.y * s);
-    }
-    dft256_full<false, true>(y, v, wt, LdsTw{twL, t, 1}, t, xrd);  // :394 (columns)
-    __syncthreads();  // every group is done with its tile before the strip is rewritten
+        for (int m = 0; m < 16; ++m) {
+            const unsigned iv = (iw[m >> 1] >> (16 * (m & 1))) & 0xffffu;
+            acc = res_add(acc, y[m], inv_n2, iv);
+            isum += iv;
+        }
+        res_block_partial<WPB>(acc, isum, a, ((size_t)z * st.B + b) * a.nblk + sub);
+    } else {
+        // amplitude replacement (:378-394), np1024.hip's form: with y the unscaled
+        // IDFT value, psi = y / N^2 and sqrt(I) psi / |psi + eps (1 + i)| =
+        // y sqrt(I) / |y + eps N^2 (1 + i)|
+        const float nn = (float)N * (float)N, epsn = st.eps * nn, epsn_im = st.eps_im * nn;
 #pragma unroll
-    for (int m = 0; m < 16; ++m) {
-        const int j = boxrow(t + 16 * m);
-        if (j >= 0) strip[j * SP + g] = v[m];
+        for (int m = 0; m < 16; ++m) {
+            const float iv = (float)((iw[m >> 1] >> (16 * (m & 1))) & 0xffffu);
+            const float2 u = y[m];
+            const float tr = u.x + epsn, ti = u.y + epsn_im;
+            const float s = amp_scale(__builtin_fmaf(tr, tr, ti * ti), iv);
+            y[m] = make_float2(u.x * s, u.y * s);
+        }
+        dft256_full<false, true>(y, v, wt, LdsTw{twL, t, 1}, t, xrd);  // :394 (columns)
+        __syncthreads();  // every group is done with its tile before the strip is rewritten
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+            const int j = boxrow(t + 16 * m, r);
+            if (j >= 0) strip[j * SP + g] = v[m];
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < tot; idx += NT) T[(size_t)(idx / GPB) * N + (idx % GPB)] = strip[(idx / GPB) * SP + (idx % GPB)];
     }
-    __syncthreads();
-    for (int idx = threadIdx.x; idx < tot; idx += NT) T[(size_t)(idx / GPB) * N + (idx % GPB)] = strip[(idx / GPB) * SP + (idx % GPB)];
 }
 
 // R2: grid (ntr * xcd_patches(B)), block NT, LDS as R1: one block per 16-row tile row of
@@ -366,6 +362,8 @@ __global__ void __launch_bounds__(n256::NT) __attribute__((amdgpu_waves_per_eu(4
 
 }  // namespace
 
+const void *residual_cols256_kernel() { return (const void *)k_cols256<ResArgs>; }
+
 // Register path for this context?  Np 256, fp32 spectrum, r < 128 (every box
 // row's frequencies inside one 256-point period), the stack in the fused
 // column layout g = 16 (the caller permutes it when this returns true).
@@ -379,11 +377,10 @@ hipError_t launch_np256_rows_cols(const DevState &st, const StepArgs &sa, const 
     if (!np256_supported(st.np, st.r, st.L, st.spec16 != nullptr) || st.meas_g != 16 || st.npart < st.nb ||
         st.npart > NT || !st.T || !st.spec)
         return hipErrorInvalidValue;
-    const size_t lds_r = (size_t)(N + GPB * XTILE_H) * sizeof(float2);
-    const size_t lds_c = (size_t)(N + std::max(st.nb * SP, GPB * XTILE_H)) * sizeof(float2);
-    const int nsr = (st.nb + GPB - 1) / GPB, Bp = xcd_patches(st.B);
-    hipLaunchKernelGGL(k_rows256_inv, dim3(nsr * Bp), dim3(NT), lds_r, s, st, sa, tw, commit ? 1 : 0);
-    hipLaunchKernelGGL(k_cols256, dim3((N / GPB) * Bp), dim3(NT), lds_c, s, st, sa, tw);
+    const size_t lds_r = lds_rows();
+    const int Bp = xcd_patches(st.B);
+    hipLaunchKernelGGL(k_rows256_inv, dim3(row_blocks(st.nb) * Bp), dim3(NT), lds_r, s, st, sa, tw, commit ? 1 : 0);
+    hipLaunchKernelGGL(k_cols256<StepArgs>, dim3(kColBlocks * Bp), dim3(NT), lds_cols(st.nb), s, st, sa, tw);
     const int ntr = (2 * st.r + 15) / kTile + 1;  // tile rows a window can span
     hipLaunchKernelGGL(k_rows256_fwd, dim3(ntr * Bp), dim3(NT), lds_r, s, st, sa, tw);
     return hipGetLastError();

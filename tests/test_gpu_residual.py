@@ -171,8 +171,8 @@ def test_one_sequence_per_block_kernels_small(which):
 
 def test_one_sequence_rows_np2700():
     """Np 2700: two box rows do not fit a 256-thread tile, so the row IDFTs run
-    one row per block (k_res_rows) and the columns two per 512-thread block
-    (k_res_cols_tiled<512, 16>; no wave holds a column of this length);
+    one row per block (k_gather_rowifft<ResArgs>) and the columns two per 512-thread block
+    (k_colpass_tiled<512, 16, ResArgs>; no wave holds a column of this length);
     the two LEDs of test_one_sequence_row_kernels_match_oracle."""
     geom = (np.array([150, 50]), np.array([150, 150]), [0, 1])
     prob, stack = _case(2700, 3000, 4, 0, 0, 1, 20261015, path=GENERAL, geom=geom)

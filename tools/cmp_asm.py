@@ -1,16 +1,23 @@
 """Device assembly of two source trees, kernel by kernel (no GPU needed): the
 check of a change that must leave every kernel's code as it was.
 
-usage: python tools/cmp_asm.py <git ref or directory of the old tree> [directory of the new tree, default .]
+usage: python tools/cmp_asm.py [--pair OLD=NEW ...] <git ref or directory of the old tree> [directory of the new tree, default .]
 
 Every fpm-opencv_amd/csrc/*.hip of both trees is compiled with the Makefile's
 flags (the max-memory-clause scheduler for MMC_FILES) to device assembly;
 functions are matched by mangled name across files, so a kernel that moved to
 another file is compared with itself.  Branch labels are renumbered in order of
-appearance; comments and debug directives are dropped.  The kernel
+appearance; comments, debug and section directives are dropped.  The kernel
 descriptors (registers, LDS, scratch) are compared as well.  Exit 1 on any
 difference.
+
+--pair OLD=NEW (repeatable; mangled names) compares a kernel whose name changed
+with its predecessor: the old tree's OLD against the new tree's NEW, with the
+name substituted in body and descriptor.  For every function that differs, the
+instruction counts of both sides and whether the descriptors are equal are
+printed.
 """
+import argparse
 import glob
 import os
 import re
@@ -45,7 +52,9 @@ def assemble(tree, out):
 
 def normalise(body):
     lines = [l.split(";")[0].rstrip() for l in body]
-    lines = [l for l in lines if l.strip() and not l.strip().startswith((".p2align", ".loc", ".file", ".cfi"))]
+    # (section directives: a function that became a template lies in a comdat section of its own)
+    drop = (".p2align", ".loc", ".file", ".cfi", ".text", ".section")
+    lines = [l for l in lines if l.strip() and not l.strip().startswith(drop)]
     text = "\n".join(lines)
     labels = {}
     for m in re.finditer(r"\.LBB\d+_\d+", text):
@@ -73,8 +82,18 @@ def functions(d):
     return out
 
 
+def instructions(body):
+    return sum(1 for l in body.splitlines() if l.startswith("\t") and not l.lstrip().startswith("."))
+
+
 def main():
-    old, new = sys.argv[1], os.path.abspath(sys.argv[2] if len(sys.argv) > 2 else ".")
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pair", action="append", default=[], metavar="OLD=NEW")
+    ap.add_argument("old")
+    ap.add_argument("new", nargs="?", default=".")
+    args = ap.parse_args()
+    old, new = args.old, os.path.abspath(args.new)
+    pairs = dict(p.split("=", 1) for p in args.pair)
     with tempfile.TemporaryDirectory() as tmp:
         if not os.path.isdir(old):
             os.mkdir(os.path.join(tmp, "old"))
@@ -85,6 +104,12 @@ def main():
             os.mkdir(dirs[-1])
             assemble(os.path.abspath(tree), dirs[-1])
         a, b = functions(dirs[0]), functions(dirs[1])
+    for o, n in pairs.items():  # the old tree's kernel under its successor's name
+        if o not in a or n not in b:
+            sys.exit(f"--pair {o}={n}: " + (f"{o} is not in the old tree" if o not in a else f"{n} is not in the new tree"))
+        f, body, desc = a.pop(o)
+        a[n] = (f, body.replace(o, n), desc.replace(o, n))
+    renamed = {n: o for o, n in pairs.items()}
     bad = 0
     for k in sorted(set(a) | set(b)):
         if k not in a or k not in b:
@@ -93,7 +118,11 @@ def main():
             continue
         same = a[k][1:] == b[k][1:]
         bad += not same
-        print("same     " if same else "DIFFERENT", f"{a[k][0]} -> {b[k][0]}", len(a[k][1].splitlines()), k)
+        print("same     " if same else "DIFFERENT", f"{a[k][0]} -> {b[k][0]}", len(a[k][1].splitlines()), k,
+              f"(was {renamed[k]})" if k in renamed else "")
+        if not same:
+            print(f"          instructions {instructions(a[k][1])} -> {instructions(b[k][1])}, descriptor",
+                  "equal" if a[k][2] == b[k][2] else "DIFFERENT")
     print(f"{len(a)} / {len(b)} functions, {bad} differ")
     sys.exit(1 if bad else 0)
 

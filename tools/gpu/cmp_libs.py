@@ -1,8 +1,10 @@
 """Bit-identity of two builds of libfpm_hip.so on the same inputs (same-box
 checks of changes that must not move a bit, e.g. a reduction rewritten with
 DPP moves).  Each library runs in its own process (FPM_HIP_LIB is read at
-import); the outputs and the context's fpm_info (the kernel selection and the
-device bytes allocated) are compared exactly.
+import); the outputs, the context's fpm_info (the kernel selection and the
+device bytes allocated) and the residual sweep's err / ref (fpm_residual after
+the run: read-only, so it disturbs nothing before it; its scratch is part of
+device_bytes, read after it) are compared exactly.
 
 usage: python tools/gpu/cmp_libs.py <lib_a.so> <lib_b.so>
 """
@@ -39,6 +41,11 @@ CASES = [  # (name, environment, geometry)
     ("np1024_lds", {"CMP_NPATCH": "1", "FPM_NO_REG1024": "1"}, (1024, 2048, 120, 3, 100)),  # LDS kernels at Np 1024
     # the one-sequence row kernels (two box rows do not fit a 256-thread tile)
     ("np2700_one_seq", {"CMP_PATH": "general", "CMP_NPATCH": "1"}, (2700, 3000, 4, 2, 100)),
+    # the residual sweep's other kernel pairs and batching (the cases above run its default)
+    ("res_lds_metric", {"FPM_RES_LDS": "1"}, G256),                                      # LDS pair, wave columns, g 16
+    ("res_one_seq_np32", {"CMP_PATH": "general", "CMP_NPATCH": "2", "FPM_RES_ONE_SEQ": "1"}, (32, 96, 6, 5, 4)),
+    ("res_batch1_np32", {"CMP_PATH": "general", "CMP_NPATCH": "2", "FPM_RES_BATCH": "1"}, (32, 96, 6, 5, 4)),
+    ("res_lds_np256_reg", {"CMP_NPATCH": "2", "FPM_RES_LDS": "1"}, (256, 768, 84, 3, 60)),
 ]
 
 CHILD = r"""
@@ -56,14 +63,16 @@ path = {"auto": fpm_amd.PATH_AUTO, "general": fpm_amd.PATH_GENERAL, "fused": fpm
 prob = fpm_amd.Problem(Np, L, order, x0, y0, r, 5, 10, n_patch=npatch, path=path,
                        flags=int(os.environ.get("CMP_FLAGS", "0")))
 with fpm_amd.Solver(prob) as s:
-    i = s.info()
     s.upload(stack)
     s.init()
     s.run(2)
     out = s.download()
+    res = s.residual()
+    i = s.info()  # device_bytes now counts the sweep's scratch
 info = np.array([i.path, i.box, i.support_px, i.device_bytes, i.wg_per_patch, i.fused_kernel, i.threads_per_wg],
                 dtype=np.int64)  # the plan and the allocation total
-np.savez(sys.argv[1], info=info, **{k: np.asarray(out[k]) for k in ("objF", "objCrop", "pupil")})
+np.savez(sys.argv[1], info=info, err=np.asarray(res["err"]), ref=np.asarray(res["ref"]),
+         **{k: np.asarray(out[k]) for k in ("objF", "objCrop", "pupil")})
 """
 
 
