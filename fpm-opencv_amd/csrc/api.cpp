@@ -98,6 +98,40 @@ int fpm_debug_get_plan(const fpm_ctx *c, int *meas_g, int *general_kind, int *re
     return FPM_OK;
 }
 
+int fpm_debug_get_maxima(const fpm_ctx *c, int *dims, float *tmax, unsigned char *dirty, float *rmax, float *pmax) {
+    if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
+    if (!c->initialized) return set_err(FPM_ERR_STATE, "fpm_debug_get_maxima before fpm_init");
+    const DevState &st = c->st;
+    if (dims) {
+        dims[0] = st.nty;
+        dims[1] = st.ntx;
+        dims[2] = st.npart;
+        dims[3] = st.rmax ? 1 : 0;
+    }
+    if (!tmax && !dirty && !rmax && !pmax) return FPM_OK;
+    if (rmax && !st.rmax) return set_err(FPM_ERR_INVAL, "a fused context keeps no tile-row maxima");
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = refuse_capture(c, "fpm_debug_get_maxima");
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const size_t B = st.B, nt = (size_t)st.ntx * st.nty, nw = (nt + 31) / 32;
+    if (tmax) HIP_TRY(hipMemcpy(tmax, st.tmax, B * nt * sizeof(float), hipMemcpyDeviceToHost));
+    if (rmax) HIP_TRY(hipMemcpy(rmax, st.rmax, B * st.nty * sizeof(float), hipMemcpyDeviceToHost));
+    if (pmax) HIP_TRY(hipMemcpy(pmax, st.pmax, B * st.npart * sizeof(float), hipMemcpyDeviceToHost));
+    if (dirty) {
+        std::vector<unsigned> bits(B * nw);
+        HIP_TRY(hipMemcpy(bits.data(), st.tdirty, bits.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+        std::memset(dirty, 0, B * nt);
+        // fused: bit k of a patch is band tile k (tilemax.hpp); general: tile k, never set
+        const BandArgs band = c->fused() ? band_of(st) : BandArgs{0, 0, st.ntx, (int)nt, 0.f};
+        for (size_t b = 0; b < B; ++b)
+            for (int k = 0; k < band.nbt; ++k)
+                if ((bits[b * nw + (k >> 5)] >> (k & 31)) & 1u)
+                    dirty[b * nt + (size_t)(band.bty0 + k / band.nbx) * st.ntx + band.btx0 + k % band.nbx] = 1;
+    }
+    return FPM_OK;
+}
+
 int fpm_runFPM(const fpm_problem *prob, int device, const uint16_t *meas, int iters, float *objF, float *objCrop,
                float *pupil, float *support) {
     fpm_ctx *c = nullptr;

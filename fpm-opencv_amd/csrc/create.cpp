@@ -73,6 +73,7 @@ Switches read_switches() {
     sw.mr_dense = on("FPM_MR_DENSE");
     sw.no_split = on("FPM_NO_SPLIT");
     sw.no_dist = on("FPM_NO_DIST");
+    sw.no_ledtab = on("FPM_NO_LEDTAB");
     sw.patch_groups = num("FPM_PATCH_GROUPS");
     sw.split = num("FPM_SPLIT");
     sw.dist = num("FPM_DIST");

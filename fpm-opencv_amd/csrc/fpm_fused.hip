@@ -796,7 +796,7 @@ hipError_t launch_fused_iteration(const DevState &st, const FusedLaunch &in, int
     const size_t lds0 = fused_lds_bytes(ks, a.band.nbt, g.n_tail_rows);
     if (lds0 > kLdsCap) return hipErrorInvalidValue;
     size_t lds;  // + the LED table when it fits
-    a.ledtab_off = ledtab_offset(lds0, in.n_order, st.L, kLdsCap, lds);
+    a.ledtab_off = ledtab_offset(lds0, in.n_order, st.L, kLdsCap, lds, in.no_ledtab);
     if (ks == 1) return launch_lds(k_fused_iteration<512, 1>, st.B, 512, lds, &a, s);
     return launch_np256_parts(ks == 4 ? k_fused_iteration<512, 4> : k_fused_iteration<512, 2>, ks, lds, &a, s);
 }

@@ -775,7 +775,7 @@ hipError_t launch_fused_dist(const DevState &st, const FusedLaunch &in, int ks, 
     const size_t lds0 = fused_dist_lds_bytes(ks, a.band.nbt, g.n_tail_rows);
     if (lds0 > kLdsCap) return hipErrorInvalidValue;
     size_t lds;  // + the LED table when it fits
-    a.ledtab_off = ledtab_offset(lds0, in.n_order, st.L, kLdsCap, lds);
+    a.ledtab_off = ledtab_offset(lds0, in.n_order, st.L, kLdsCap, lds, in.no_ledtab);
     return launch_np256_parts(ks == 8 ? k_fused_dist<8> : ks == 4 ? k_fused_dist<4> : k_fused_dist<2>, ks, lds, &a, s);
 }
 

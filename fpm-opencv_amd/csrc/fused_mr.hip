@@ -465,7 +465,8 @@ hipError_t launch_fused_mr_iteration(const DevState &st, const FusedLaunch &in, 
     for (int i = 0; i < fm::GPW; ++i)
         a.xg[i] = a.xw == fm::XW_SHIFT ? fm::XG_SHIFT[i] : i * (a.xw == fm::XW_STRIDE ? 106 : fm::XT);
     size_t lds;  // the kernel's own LDS + the LED table when it fits
-    a.ledtab_off = ledtab_offset(mr_lds_bytes(st.nb, a.band.nbt, a.xw, a.tld), in.n_order, st.L, kLdsCap, lds);
+    a.ledtab_off = ledtab_offset(mr_lds_bytes(st.nb, a.band.nbt, a.xw, a.tld), in.n_order, st.L, kLdsCap, lds,
+                                 in.no_ledtab);
     return launch_lds(k_fused_mr, st.B, fm::NT, lds, &a, s);
 }
 

@@ -435,7 +435,8 @@ hipError_t launch_fused_s90_iteration(const DevState &st, const FusedLaunch &in,
     for (int i = 0; i < f90::GPW; ++i) a.xg[i] = fast ? f90::XG_FAST[i] : i * f90::XT;
     a.tld = fast ? f90::TLD_FAST : f90::TLD;
     size_t lds;  // the kernel's own LDS + the LED table when it fits
-    a.ledtab_off = ledtab_offset(s90_lds_bytes(st.nb, a.nbt, a.xw, a.tld), in.n_order, st.L, kLdsCap, lds);
+    a.ledtab_off = ledtab_offset(s90_lds_bytes(st.nb, a.nbt, a.xw, a.tld), in.n_order, st.L, kLdsCap, lds,
+                                 in.no_ledtab);
     return launch_lds(k_fused_s90, st.B, f90::NT, lds, &a, s);
 }
 

@@ -19,6 +19,7 @@ struct Switches {
     bool no_wave_cols, no_crop4k;             // FPM_NO_WAVE_COLS, FPM_NO_CROP4K
     bool s90_dense, mr_dense;                 // FPM_S90_DENSE, FPM_MR_DENSE
     bool no_split, no_dist;                   // FPM_NO_SPLIT, FPM_NO_DIST
+    bool no_ledtab;                           // FPM_NO_LEDTAB: the fused kernels read the global LED tables
     int patch_groups, split, dist;            // FPM_PATCH_GROUPS, FPM_SPLIT, FPM_DIST: the value (>= 0), -1 = unset
     bool res_lds;                             // FPM_RES_LDS: the residual's LDS kernel pair where the register pair applies
     bool res_one_seq;                         // FPM_RES_ONE_SEQ: the LDS pair's one-sequence-per-block kernels at any size

@@ -46,9 +46,11 @@ struct LedTab {
 // becomes the launch's dynamic LDS size.  A centre (yc, xc) lies in [0, L)
 // (fpm_create keeps every crop window inside the spectrum) and is packed as
 // two unsigned 16-bit fields, so the table is used only for L <= 65536.
-inline int ledtab_offset(size_t lds, int n_order, int L, size_t cap, size_t &total) {
+// off_switch: FPM_NO_LEDTAB=1, the kernel reads the global tables as if the
+// table did not fit (it does not for more than ~20 000 entries of order[]).
+inline int ledtab_offset(size_t lds, int n_order, int L, size_t cap, size_t &total, bool off_switch) {
     const size_t off = (lds + 7) & ~(size_t)7;
-    if (n_order > 0 && L <= 65536 && off + (size_t)n_order * 8 <= cap) {
+    if (!off_switch && n_order > 0 && L <= 65536 && off + (size_t)n_order * 8 <= cap) {
         total = off + (size_t)n_order * 8;
         return (int)off;
     }

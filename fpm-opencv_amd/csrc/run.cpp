@@ -234,7 +234,7 @@ int fpm_run(fpm_ctx *c, int iters) {
     if (use_graph && (rc = general_graph(c))) return rc;
     const bool last_only = (c->prob.flags & FPM_FLAG_OBJCROP_LAST_ONLY) != 0;
     const FusedLaunch in{c->meas, c->order_dev, c->x0_dev, c->y0_dev, c->prob.n_order, c->tw_np, c->dbg,
-                         c->kernel == Kernel::Np90 ? c->sw.s90_dense : c->sw.mr_dense};
+                         c->kernel == Kernel::Np90 ? c->sw.s90_dense : c->sw.mr_dense, c->sw.no_ledtab};
     const hipEvent_t *ev = c->evpool.data();
     HIP_TRY(hipEventRecord(ev[0], c->stream));
     for (int it = 0; it < iters; ++it) {

@@ -52,7 +52,8 @@ HIP_SYMBOLS = (
     "fpm_get_clock", "fpm_residual",
 )
 # test-only entry points (include/fpm_hip_debug.h)
-HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan")
+HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan",
+                     "fpm_debug_get_maxima")
 # fpm_debug_get_plan: general_kind / residual_kind values
 GENERAL_REG1024, GENERAL_REG256, GENERAL_LDS = 0, 1, 2
 RESIDUAL_REG256, RESIDUAL_LDS = 0, 1
@@ -134,6 +135,7 @@ def load_library(path: str = HIP_LIB):
         "fpm_abi_version": (C.c_int, []),
         "fpm_debug_set_stall": (C.c_int, [vp, C.c_int]),
         "fpm_debug_get_plan": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "fpm_debug_get_maxima": (C.c_int, [vp, C.POINTER(C.c_int), f32p, C.POINTER(C.c_uint8), f32p, f32p]),
         "fpm_get_timing": (C.c_int, [vp, C.POINTER(fpm_timing)]),
         "fpm_get_clock": (C.c_int, [vp, C.POINTER(fpm_clock)]),
         "fpm_residual": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -336,6 +338,24 @@ class Solver:
         g, k, r = C.c_int(), C.c_int(), C.c_int()
         _check(_lib.fpm_debug_get_plan(self._h, C.byref(g), C.byref(k), C.byref(r)))
         return dict(meas_g=g.value, general_kind=k.value, residual_kind=r.value)
+
+    def debug_maxima(self) -> dict:
+        """Test-only (include/fpm_hip_debug.h): the carried max|objF| / max|P|
+        bookkeeping after synchronising the stream, in full tile coordinates of
+        the centred spectrum: tmax float32 [B][nty][ntx], dirty bool
+        [B][nty][ntx], rmax float32 [B][nty] (None on a fused context), pmax
+        float32 [B][npart].  Read-only."""
+        dims = (C.c_int * 4)()
+        _check(_lib.fpm_debug_get_maxima(self._h, dims, None, None, None, None))
+        nty, ntx, npart, has_rmax = (int(v) for v in dims)
+        B = self.prob.n_patch
+        tmax = np.empty((B, nty, ntx), np.float32)
+        dirty = np.empty((B, nty, ntx), np.uint8)
+        rmax = np.empty((B, nty), np.float32) if has_rmax else None
+        pmax = np.empty((B, npart), np.float32)
+        _check(_lib.fpm_debug_get_maxima(self._h, dims, _f32p(tmax), dirty.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                         _f32p(rmax), _f32p(pmax)))
+        return dict(tmax=tmax, dirty=dirty.astype(bool), rmax=rmax, pmax=pmax)
 
     def timing(self) -> fpm_timing:
         t = fpm_timing()

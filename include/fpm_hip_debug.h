@@ -1,7 +1,8 @@
 /* fpm_hip_debug.h -- test-only entry points of libfpm_hip.so (not part of the
  * drop-in boundary include/fpm_hip.h): device helpers exposed so the tests can
- * pin them on extreme inputs no valid stack reaches, and a fault injector for
- * the multi-workgroup handoffs. */
+ * pin them on extreme inputs no valid stack reaches, a fault injector for
+ * the multi-workgroup handoffs, and read-backs of what a context planned and
+ * of the maxima it carries between LED steps. */
 #ifndef FPM_HIP_DEBUG_H
 #define FPM_HIP_DEBUG_H
 
@@ -39,6 +40,22 @@ int fpm_debug_set_stall(fpm_ctx *ctx, int led);
  * step kernels (0 Np 1024 register, 1 Np 256 register, 2 LDS; -1 on a fused
  * context); residual_kind = fpm_residual's kernel pair (0 register, 1 LDS). */
 int fpm_debug_get_plan(const fpm_ctx *ctx, int *meas_g, int *general_kind, int *residual_kind);
+
+/* The max|objF| / max|P| bookkeeping a context carries from one LED step and
+ * one launch to the next (fpm_state.hpp), read back after synchronising the
+ * context's stream; needs fpm_init.  Read-only: the device state is not
+ * touched.  Any pointer may be NULL.
+ *   dims[4]             nty, ntx, npart, has_rmax (size the other arrays with a
+ *                       first call that passes only dims)
+ *   tmax  [B][nty][ntx] max|spec| of each 16 x 16 tile of the centred spectrum
+ *   dirty [B][nty][ntx] 1: the tile's tmax is only an upper bound (fused
+ *                       kernels; they keep the bits indexed by live-band tile,
+ *                       converted here: a tile outside the band is clean, and
+ *                       its tmax is the 0 fpm_init wrote)
+ *   rmax  [B][nty]      maximum of each tile row (general path: has_rmax = 1;
+ *                       FPM_ERR_INVAL when asked of a fused context)
+ *   pmax  [B][npart]    partial maxima of |P| */
+int fpm_debug_get_maxima(const fpm_ctx *ctx, int *dims, float *tmax, unsigned char *dirty, float *rmax, float *pmax);
 
 #ifdef __cplusplus
 }

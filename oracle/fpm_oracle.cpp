@@ -21,6 +21,7 @@
 // C ABI (ctypes from tests / bench):
 //   int oracle_run_fpm(...)        one patch
 //   int oracle_run_fpm_batch(...)  n_patch patches on n_threads std::threads
+//   int oracle_run_fpm_at / oracle_run_fpm_batch_at(...)  the same with init_pos
 //   int oracle_fft2(...)           KAT hook for the FFT
 #include <cmath>
 #include <complex>
@@ -124,6 +125,7 @@ struct Params {
     const int *order, *x0, *y0;
     double d1, d2, eps;
     int all_ch;  // 1: cv::add(c2, double) acts on both channels (OpenCV default)
+    int init_pos;  // position in order[] of the LED that seeds the spectrum (the reference: 1)
 };
 
 int run_one(const Params &P, double *objF_out, double *objCrop_out, double *pupil_out) {
@@ -131,6 +133,7 @@ int run_one(const Params &P, double *objF_out, double *objCrop_out, double *pupi
     const size_t NN = (size_t)np * np, LL = (size_t)L * L;
     Fft fnp(np), fl(L);
     if (!fnp.ok() || !fl.ok() || (np & 1) || (L & 1) || P.n_order < 2) return -22;
+    if (P.init_pos < 0 || P.init_pos >= P.n_order) return -22;
     // :302-313 support = filled disk at (Np/2, Np/2), fftShift
     std::vector<cplx> planes0(NN, 0.0), support, pupil;
     const int c = np / 2;
@@ -139,8 +142,8 @@ int run_one(const Params &P, double *objF_out, double *objCrop_out, double *pupi
             if ((x - c) * (x - c) + (y - c) * (y - c) <= P.r * P.r) planes0[(size_t)y * np + x] = 1.0;
     fftshift(planes0, support, np, np);
     pupil = support;
-    // :319-327
-    const uint16_t *I0 = P.stack + (size_t)P.order[1] * NN;
+    // :319-327 (sortedIndicies.at(1) in the reference)
+    const uint16_t *I0 = P.stack + (size_t)P.order[P.init_pos] * NN;
     std::vector<cplx> ci(NN), tmp, tmp2;
     for (size_t i = 0; i < NN; ++i) ci[i] = std::sqrt((double)I0[i]);
     fft2(ci, np, np, false, 1.0, fnp, fnp);
@@ -240,20 +243,30 @@ int run_one(const Params &P, double *objF_out, double *objCrop_out, double *pupi
 
 extern "C" {
 
-// stack: uint16 [n_stack][Np][Np]; outputs complex128 interleaved (may be NULL)
+// stack: uint16 [n_stack][Np][Np]; outputs complex128 interleaved (may be NULL);
+// init_pos: the position in order[] whose LED seeds the spectrum
+int oracle_run_fpm_at(int np, int L, int n_stack, const uint16_t *stack, int n_order, const int *order,
+                      const int *x0, const int *y0, int radius, double delta1, double delta2, double eps, int iters,
+                      int all_channels, int init_pos, double *objF, double *objCrop, double *pupil) {
+    Params P{np, L, n_stack, n_order, radius, iters, stack, order, x0, y0, delta1, delta2, eps, all_channels,
+             init_pos};
+    return run_one(P, objF, objCrop, pupil);
+}
+
+// the reference's init: sortedIndicies.at(1)
 int oracle_run_fpm(int np, int L, int n_stack, const uint16_t *stack, int n_order, const int *order,
                    const int *x0, const int *y0, int radius, double delta1, double delta2, double eps, int iters,
                    int all_channels, double *objF, double *objCrop, double *pupil) {
-    Params P{np, L, n_stack, n_order, radius, iters, stack, order, x0, y0, delta1, delta2, eps, all_channels};
-    return run_one(P, objF, objCrop, pupil);
+    return oracle_run_fpm_at(np, L, n_stack, stack, n_order, order, x0, y0, radius, delta1, delta2, eps, iters,
+                             all_channels, 1, objF, objCrop, pupil);
 }
 
 // n_patch patches, stack LED-major [n_stack][n_patch][Np][Np] (the HIP layout);
 // patches are spread over n_threads std::threads.  Outputs per patch.
-int oracle_run_fpm_batch(int np, int L, int n_stack, int n_patch, const uint16_t *stack, int n_order,
-                         const int *order, const int *x0, const int *y0, int radius, double delta1, double delta2,
-                         double eps, int iters, int all_channels, int n_threads, double *objF, double *objCrop,
-                         double *pupil) {
+int oracle_run_fpm_batch_at(int np, int L, int n_stack, int n_patch, const uint16_t *stack, int n_order,
+                            const int *order, const int *x0, const int *y0, int radius, double delta1,
+                            double delta2, double eps, int iters, int all_channels, int init_pos, int n_threads,
+                            double *objF, double *objCrop, double *pupil) {
     const size_t NN = (size_t)np * np, LL = (size_t)L * L;
     std::vector<int> rc(n_patch, 0);
     auto work = [&](int t) {
@@ -262,7 +275,7 @@ int oracle_run_fpm_batch(int np, int L, int n_stack, int n_patch, const uint16_t
             for (int s = 0; s < n_stack; ++s)
                 std::memcpy(&own[(size_t)s * NN], stack + ((size_t)s * n_patch + b) * NN, NN * sizeof(uint16_t));
             Params P{np, L, n_stack, n_order, radius, iters, own.data(), order, x0, y0, delta1, delta2, eps,
-                     all_channels};
+                     all_channels, init_pos};
             rc[b] = run_one(P, objF ? objF + 2 * LL * b : nullptr, objCrop ? objCrop + 2 * LL * b : nullptr,
                             pupil ? pupil + 2 * NN * b : nullptr);
         }
@@ -274,6 +287,14 @@ int oracle_run_fpm_batch(int np, int L, int n_stack, int n_patch, const uint16_t
     for (int v : rc)
         if (v) return v;
     return 0;
+}
+
+int oracle_run_fpm_batch(int np, int L, int n_stack, int n_patch, const uint16_t *stack, int n_order,
+                         const int *order, const int *x0, const int *y0, int radius, double delta1, double delta2,
+                         double eps, int iters, int all_channels, int n_threads, double *objF, double *objCrop,
+                         double *pupil) {
+    return oracle_run_fpm_batch_at(np, L, n_stack, n_patch, stack, n_order, order, x0, y0, radius, delta1, delta2,
+                                   eps, iters, all_channels, 1, n_threads, objF, objCrop, pupil);
 }
 
 // KAT hook: in-place 2-D DFT (complex128 interleaved), inverse scaled by 1/(rows*cols)

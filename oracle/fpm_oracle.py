@@ -63,19 +63,20 @@ def disk_support(np_: int, radius: int) -> np.ndarray:
 
 
 def _fft2(a):
-    # cvComplex fft2: unscaled forward DFT (fpmMain.cpp:325,394)
-    return np.fft.fft2(a)
+    # cvComplex fft2: unscaled forward DFT (fpmMain.cpp:325,394); the result
+    # keeps the input's precision (run_fpm's dtype)
+    return np.fft.fft2(a).astype(a.dtype, copy=False)
 
 
 def _ifft2(a):
     # cvComplex ifft2: inverse DFT scaled by 1/(rows*cols) (fpmMain.cpp:365)
-    return np.fft.ifft2(a)
+    return np.fft.ifft2(a).astype(a.dtype, copy=False)
 
 
 def run_fpm(stack, order, x0, y0, np_: int, L: int, radius: int,
             delta1: float, delta2: float, iters: int,
             eps: float = float(np.float32(1e-10)), record=None,
-            all_channels: bool = True):
+            all_channels: bool = True, init_pos: int = 1, dtype=np.complex128):
     """Restatement of ``runFPM`` (fpmMain.cpp:274-498) for ONE patch.
 
     Parameters mirror the ``FPM_Dataset`` fields runFPM reads
@@ -91,27 +92,38 @@ def run_fpm(stack, order, x0, y0, np_: int, L: int, radius: int,
     eps     : ``float eps = 1e-10`` (fpmMain.h:99).
     all_channels : OpenCV scalar unrolling (module docstring): a double added
               to / multiplied into a CV_64FC2 array acts on both channels.
+    init_pos : position in ``order`` of the LED whose image seeds the spectrum
+              (the reference hard-codes 1, ``sortedIndicies.at(1)``; the C
+              boundary takes it as ``fpm_problem.init_pos``).
+    dtype   : ``np.complex128`` (the oracle) or ``np.complex64``: the same
+              operations with the state and every intermediate rounded to
+              single precision, the transforms included -- the fp32 drift of
+              the algorithm itself, which decides whether a case is well enough
+              conditioned for the fp32 device path (tests/test_schedules.py).
 
     Returns dict(objF=un-centred L x L spectrum, objCrop=IDFT(objF)/L^2,
     pupil=centred Np x Np pupil (fpmMain.cpp:496), support=un-centred S).
     """
     stack = np.asarray(stack)
     order = [int(i) for i in order]
+    ct = np.dtype(dtype)
+    rt = np.float64 if ct == np.complex128 else np.float32
+    assert ct in (np.dtype(np.complex128), np.dtype(np.complex64)), ct
     # cv::add(c2, s) with s a double: (re + s, im + s) when unrolled to every
     # channel, (re + s, im) under the real-channel-only assumption
     cs = (1 + 1j) if all_channels else 1.0
     S = disk_support(np_, radius)                       # :302-313
-    pupil = S.astype(np.complex128)                     # mergeUMat(planes)
+    pupil = S.astype(ct)                                # mergeUMat(planes)
     support = pupil.copy()                              # :313
 
     # :319-327  A = sqrt(I[sortedIndicies[1]]); O = fftShift(fft2(A) * S)
-    amp0 = np.sqrt(stack[order[1]].astype(np.float64))
-    complex_i = _fft2(amp0.astype(np.complex128))
+    amp0 = np.sqrt(stack[order[init_pos]].astype(rt))
+    complex_i = _fft2(amp0.astype(ct))
     complex_i = complex_i * support
     complex_i = fftshift2(complex_i)
 
     # :330-343 place in the centre of an L x L zero spectrum, then un-centre
-    objF = np.zeros((L, L), np.complex128)
+    objF = np.zeros((L, L), ct)
     c0 = L // 2 - np_ // 2
     objF[c0:c0 + np_, c0:c0 + np_] = complex_i
     objF = fftshift2(objF)
@@ -124,7 +136,7 @@ def run_fpm(stack, order, x0, y0, np_: int, L: int, radius: int,
             objfcrop = fftshift2(objF_c[ys:ys + np_, xs:xs + np_])      # :361
             objfcropP = objfcrop * pupil                                # :364
             objcropP = _ifft2(objfcropP)                                # :365
-            object_amp = np.sqrt(stack[led].astype(np.float64))         # :378-387
+            object_amp = np.sqrt(stack[led].astype(rt))                 # :378-387
             tmp1 = objcropP + eps * cs                                  # :390
             tmp3 = np.abs(tmp1)                                         # :391
             tmp1 = objcropP / tmp3                                      # :392
@@ -151,9 +163,10 @@ def run_fpm(stack, order, x0, y0, np_: int, L: int, radius: int,
             pupil = pupil + tmp2                                        # :475
             if record is not None:
                 record.append((led, objF.copy(), pupil.copy()))
-        objCrop = np.fft.ifft2(objF)                    # :481 DFT_INVERSE|DFT_SCALE
+            assert objF.dtype == ct and pupil.dtype == ct, (objF.dtype, pupil.dtype)
+        objCrop = _ifft2(objF)                          # :481 DFT_INVERSE|DFT_SCALE
     if objCrop is None:
-        objCrop = np.fft.ifft2(objF)
+        objCrop = _ifft2(objF)
     return dict(objF=objF, objCrop=objCrop, pupil=fftshift2(pupil),
                 support=support)
 

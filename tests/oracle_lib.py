@@ -18,11 +18,11 @@ def load():
             subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "liboracle.so"])
         lib = C.CDLL(ORACLE_SO)
         ip, dp, u16p = C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_uint16)
-        lib.oracle_run_fpm.argtypes = [C.c_int, C.c_int, C.c_int, u16p, C.c_int, ip, ip, ip, C.c_int,
-                                       C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, dp, dp, dp]
-        lib.oracle_run_fpm_batch.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, u16p, C.c_int, ip, ip, ip,
+        lib.oracle_run_fpm_at.argtypes = [C.c_int, C.c_int, C.c_int, u16p, C.c_int, ip, ip, ip, C.c_int,
+                                       C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_int, dp, dp, dp]
+        lib.oracle_run_fpm_batch_at.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, u16p, C.c_int, ip, ip, ip,
                                              C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int,
-                                             C.c_int, dp, dp, dp]
+                                             C.c_int, C.c_int, dp, dp, dp]
         lib.oracle_fft2.argtypes = [dp, C.c_int, C.c_int, C.c_int]
         _lib = lib
     return _lib
@@ -32,9 +32,11 @@ def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int))
 
 
-def run_fpm(stack, order, x0, y0, np_, L, r, d1, d2, iters, eps=float(np.float32(1e-10)), all_channels=True):
+def run_fpm(stack, order, x0, y0, np_, L, r, d1, d2, iters, eps=float(np.float32(1e-10)), all_channels=True,
+            init_pos=1):
     """One patch; stack uint16 [n_stack][Np][Np]. Returns complex128 outputs.
-    all_channels=False restates FPM_FLAG_SCALAR_RE_ONLY (fpm_oracle.cpp header)."""
+    all_channels=False restates FPM_FLAG_SCALAR_RE_ONLY (fpm_oracle.cpp header);
+    init_pos is fpm_problem.init_pos (the reference: 1)."""
     lib = load()
     st = np.ascontiguousarray(stack, np.uint16)
     order, x0, y0 = (np.ascontiguousarray(v, np.int32) for v in (order, x0, y0))
@@ -42,15 +44,16 @@ def run_fpm(stack, order, x0, y0, np_, L, r, d1, d2, iters, eps=float(np.float32
     objCrop = np.zeros((L, L), np.complex128)
     pupil = np.zeros((np_, np_), np.complex128)
     dp = C.POINTER(C.c_double)
-    rc = lib.oracle_run_fpm(np_, L, len(x0), st.ctypes.data_as(C.POINTER(C.c_uint16)), len(order), _ip(order),
-                            _ip(x0), _ip(y0), r, d1, d2, eps, iters, int(all_channels), objF.ctypes.data_as(dp),
+    rc = lib.oracle_run_fpm_at(np_, L, len(x0), st.ctypes.data_as(C.POINTER(C.c_uint16)), len(order), _ip(order),
+                            _ip(x0), _ip(y0), r, d1, d2, eps, iters, int(all_channels), int(init_pos),
+                            objF.ctypes.data_as(dp),
                             objCrop.ctypes.data_as(dp), pupil.ctypes.data_as(dp))
     assert rc == 0, rc
     return dict(objF=objF, objCrop=objCrop, pupil=pupil)
 
 
 def run_fpm_batch(stack, order, x0, y0, np_, L, r, d1, d2, iters, threads, outputs=True,
-                  eps=float(np.float32(1e-10)), all_channels=True, pupil=False, objF=False):
+                  eps=float(np.float32(1e-10)), all_channels=True, pupil=False, objF=False, init_pos=1):
     """stack uint16 [n_stack][B][Np][Np]; B patches on `threads` threads.
     Returns objCrop [B][L][L] (None when outputs=False), or with pupil=True
     (objF=True) a dict of objCrop and pupil [B][Np][Np] (centred, like
@@ -64,8 +67,9 @@ def run_fpm_batch(stack, order, x0, y0, np_, L, r, d1, d2, iters, threads, outpu
     pupil = pupil or objF
     pup = np.zeros((B, np_, np_), np.complex128) if (outputs and pupil) else None
     oF = np.zeros((B, L, L), np.complex128) if (outputs and objF) else None
-    rc = lib.oracle_run_fpm_batch(np_, L, len(x0), B, st.ctypes.data_as(C.POINTER(C.c_uint16)), len(order),
-                                  _ip(order), _ip(x0), _ip(y0), r, d1, d2, eps, iters, int(all_channels), threads,
+    rc = lib.oracle_run_fpm_batch_at(np_, L, len(x0), B, st.ctypes.data_as(C.POINTER(C.c_uint16)), len(order),
+                                  _ip(order), _ip(x0), _ip(y0), r, d1, d2, eps, iters, int(all_channels), int(init_pos),
+                                  threads,
                                   oF.ctypes.data_as(dp) if oF is not None else None,
                                   objCrop.ctypes.data_as(dp) if outputs else None,
                                   pup.ctypes.data_as(dp) if pup is not None else None)
