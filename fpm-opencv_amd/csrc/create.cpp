@@ -9,7 +9,9 @@
 #include <cstring>
 #include <memory>
 
+#include "../../include/fpm_hip_debug.h"
 #include "ctx.hpp"
+#include "fft_inplace.hpp"
 
 using namespace fpm;
 
@@ -80,6 +82,7 @@ Switches read_switches() {
     sw.res_lds = on("FPM_RES_LDS");
     sw.res_one_seq = on("FPM_RES_ONE_SEQ");
     sw.res_batch = num("FPM_RES_BATCH");
+    sw.one_seq = on("FPM_ONE_SEQ");
     return sw;
 }
 
@@ -126,8 +129,9 @@ int validate(const fpm_problem *p) {
     return FPM_OK;
 }
 
-// a gfx950 device; makes it current and reports its CU count
-int check_device(int device, int *n_cu) {
+// a gfx950 device; makes it current and reports its CU count and the LDS a
+// workgroup can have
+int check_device(int device, int *n_cu, size_t *lds_limit) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return set_err(FPM_ERR_NODEV, "no HIP device visible");
@@ -138,6 +142,7 @@ int check_device(int device, int *n_cu) {
         return set_err(FPM_ERR_NODEV, "device %d is %s, this library is built for gfx950", device, pr.gcnArchName);
     HIP_TRY(hipSetDevice(device));
     *n_cu = pr.multiProcessorCount;
+    *lds_limit = std::max(pr.sharedMemPerBlock, pr.maxSharedMemoryPerMultiProcessor);  // one workgroup may take a CU's
     return FPM_OK;
 }
 
@@ -182,11 +187,28 @@ void plan_state(fpm_ctx *c) {
     st.sx1 = std::min(st.sx1, L - 1);
 }
 
+// a planned launch within the LDS a workgroup can have (dynamic plus the kernel's own)
+int lds_fits(const fpm_ctx *c, const char *what, const StepKernel &k, size_t lds_limit) {
+    if (k.lds_total() <= lds_limit) return FPM_OK;
+    return set_err(FPM_ERR_INVAL, "Np=%d r=%d: the %s kernel needs %zu B of LDS (%zu dynamic + %zu static), the "
+                   "device offers %zu", c->prob.np, c->prob.na_radius, what, k.lds_total(), k.lds, k.lds_static,
+                   lds_limit);
+}
+
+// the sweep's LDS pair (the register pair's LDS does not grow with the problem)
+int residual_lds_fits(const fpm_ctx *c, size_t lds_limit) {
+    if (c->rplan.kind != ResidualPlan::Lds) return FPM_OK;
+    const int rc = lds_fits(c, "residual row", c->rplan.rows, lds_limit);
+    return rc ? rc : lds_fits(c, "residual column", c->rplan.cols, lds_limit);
+}
+
 // Everything a context is, decided from the validated problem (c->prob with
-// its arrays), the switches (c->sw) and the device's CU count before anything
-// is created: no HIP call, no device memory.  Refuses a fused path that this
-// geometry or fp16 spectrum storage does not have.
-int plan_context(fpm_ctx *c, int n_cu) {
+// its arrays), the switches (c->sw), the device's CU count and its LDS per
+// workgroup before anything is created: no HIP call, no device memory.
+// Refuses a fused path that this geometry or fp16 spectrum storage does not
+// have, and a size whose planned step or sweep kernel needs more LDS than the
+// device offers (Np 10240: DESIGN.md section 4.7).
+int plan_context(fpm_ctx *c, int n_cu, size_t lds_limit) {
     const fpm_problem &p = c->prob;
     const Switches &sw = c->sw;
     const int np = p.np, L = p.nlarge, r = p.na_radius, nb = 2 * r + 1, B = p.n_patch;
@@ -229,7 +251,7 @@ int plan_context(fpm_ctx *c, int n_cu) {
         st.npart = 1;
         c->meas_g = c->row().meas_g < 0 ? np : c->row().meas_g;
         c->rplan = plan_residual(st, c->pl_np, p.n_order, c->meas_g, fp16, sw);
-        return FPM_OK;
+        return residual_lds_fits(c, lds_limit);
     }
     // Np 1024 general path: register row/column kernels reading the stack
     // transposed; Np 256 beyond the fused kernels' radius: register kernels
@@ -255,7 +277,20 @@ int plan_context(fpm_ctx *c, int n_cu) {
     c->ngroups = sw.patch_groups >= 0 ? sw.patch_groups : (reg ? 2 : 1);
     c->ngroups = std::max(1, std::min({c->ngroups, B, (int)fpm_ctx::kMaxGroups}));
     c->rplan = plan_residual(st, c->pl_np, p.n_order, c->meas_g, fp16, sw);
-    return FPM_OK;
+    // what each patch group's LED step launches: it reads the sizes only
+    for (int g = 0; g < c->ngroups; ++g) {
+        DevState v = st;
+        v.B = (g + 1) * B / c->ngroups - g * B / c->ngroups;
+        c->gplan[g] = plan_general_step(v, c->general_kind, c->pl_np, sw);
+    }
+    int rc = FPM_OK;
+    for (int g = 0; !reg && g < c->ngroups; ++g) {  // the register kernels' LDS does not grow with the problem
+        const GeneralPlan &gp = c->gplan[g];
+        if ((rc = lds_fits(c, "row IDFT", gp.k1, lds_limit)) || (rc = lds_fits(c, "column", gp.k2, lds_limit)) ||
+            (rc = lds_fits(c, "row DFT / update", gp.k3, lds_limit)))
+            return rc;
+    }
+    return residual_lds_fits(c, lds_limit);
 }
 
 // the run stream, the buffers and the patch groups' streams the plan names
@@ -337,11 +372,13 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
     if (!out) return set_err(FPM_ERR_INVAL, "null out");
     *out = nullptr;
     int rc = validate(prob), n_cu = 0;
-    if (rc || (rc = check_device(device, &n_cu))) return rc;
+    size_t lds_limit = 0;
+    if (rc || (rc = check_device(device, &n_cu, &lds_limit))) return rc;
 
     std::unique_ptr<fpm_ctx> c(new fpm_ctx());
     c->prob = *prob;
     c->device = device;
+    c->lds_limit = lds_limit;
     c->sw = read_switches();
     c->order.assign(prob->order, prob->order + prob->n_order);
     c->x0.assign(prob->crop_x0, prob->crop_x0 + prob->n_stack);
@@ -350,10 +387,11 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
     c->prob.crop_x0 = c->x0.data();
     c->prob.crop_y0 = c->y0.data();
 
-    if ((rc = plan_context(c.get(), n_cu)) || (rc = allocate(c.get())) || (rc = upload_tables(c.get()))) return rc;
+    if ((rc = plan_context(c.get(), n_cu, lds_limit)) || (rc = allocate(c.get())) || (rc = upload_tables(c.get())))
+        return rc;
     if (!c->fused())
-        for (int g = 0; g < c->ngroups; ++g)
-            c->gplan[g] = plan_general_step(group_view(c.get(), g), c->general_kind, c->pl_np, c->sw);
+        for (int g = 0; g < c->ngroups && c->general_kind == GeneralPlan::Lds; ++g)
+            HIP_TRY(allow_large_lds({&c->gplan[g].k1, &c->gplan[g].k2, &c->gplan[g].k3}, lds_limit));
     *out = c.release();
     return FPM_OK;
 }
@@ -368,6 +406,81 @@ void fpm_destroy(fpm_ctx *c) {
 int fpm_set_stream(fpm_ctx *c, void *s) {
     if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
     c->stream = s ? (hipStream_t)s : c->own_stream;
+    return FPM_OK;
+}
+
+// ---- the planner's read-backs (include/fpm_hip_debug.h) ----------------------------
+static fpm_ladder_kernel ladder_kernel(const StepKernel &k, int e, int cw, size_t lds_static) {
+    fpm_ladder_kernel o;
+    o.generation = cw ? FPM_LADDER_WAVE : e ? FPM_LADDER_TILED : FPM_LADDER_ONE_SEQ;
+    o.tile = cw ? cw : e ? k.arg : 0;
+    o.threads = (int)k.block.x;
+    o.e = cw ? kWaveElems : e;
+    o.grid_x = (int)k.grid.x;
+    o.grid_y = (int)k.grid.y;
+    o.lds_dynamic = (int)k.lds;
+    o.lds_static = (int)lds_static;
+    return o;
+}
+
+int fpm_debug_plan_ladder(int np, int nb, int B, int step, int no_wave_cols, int one_seq, fpm_ladder *out) {
+    if (!out || np < 2 || nb < 1 || nb > np || B < 1) return set_err(FPM_ERR_INVAL, "fpm_debug_plan_ladder: bad argument");
+    FftPlan pl;
+    if (!make_plan(np, &pl)) return set_err(FPM_ERR_INVAL, "Np=%d is not 2^a 3^b 5^c", np);
+    Switches sw{};
+    sw.no_wave_cols = no_wave_cols != 0;
+    sw.one_seq = sw.res_one_seq = one_seq != 0;
+    DevState st{};
+    st.np = np;
+    st.nb = nb;
+    st.B = B;
+    StepKernel rows, cols;
+    LdsLadder l;
+    size_t row_static;
+    if (step) {
+        const GeneralPlan p = plan_general_step(st, GeneralPlan::Lds, pl, sw);
+        l = p.ladder, rows = p.k1, cols = p.k2;
+        row_static = std::max(p.k1.lds_static, p.k3.lds_static);
+    } else {
+        l = plan_lds_ladder(pl, np, nb, B, sw, false);
+        residual_lds_kernels(l, rows, cols);
+        row_static = rows.lds_static;
+    }
+    out->rows = ladder_kernel(rows, l.row_e, 0, row_static);
+    out->cols = ladder_kernel(cols, l.col_e, l.cw, cols.lds_static);
+    return FPM_OK;
+}
+
+// the kLds constant of a planned kernel against the __shared__ bytes its code object declares
+static int static_lds_matches(const StepKernel &k) {
+    hipFuncAttributes a;
+    HIP_TRY(hipFuncGetAttributes(&a, k.fn));
+    if (a.sharedSizeBytes != k.lds_static)
+        return set_err(FPM_ERR_STATE, "a kernel declares %zu B of static LDS, its constant says %zu",
+                       (size_t)a.sharedSizeBytes, k.lds_static);
+    return FPM_OK;
+}
+
+int fpm_debug_get_ladder(const fpm_ctx *c, int residual, fpm_ladder *out) {
+    if (!c || !out) return set_err(FPM_ERR_INVAL, "null argument");
+    if (c->fused() || c->general_kind != GeneralPlan::Lds)
+        return set_err(FPM_ERR_INVAL, "the LED step of this context does not run the LDS kernel ladder");
+    if (residual) {
+        const ResidualPlan &p = c->rplan;
+        if (p.kind != ResidualPlan::Lds) return set_err(FPM_ERR_INVAL, "the residual sweep runs the register pair");
+        HIP_TRY(hipSetDevice(c->device));
+        int rc = static_lds_matches(p.rows);
+        if (rc || (rc = static_lds_matches(p.cols))) return rc;
+        out->rows = ladder_kernel(p.rows, p.ladder.row_e, 0, p.rows.lds_static);
+        out->cols = ladder_kernel(p.cols, p.ladder.col_e, p.ladder.cw, p.cols.lds_static);
+        return FPM_OK;
+    }
+    const GeneralPlan &p = c->gplan[0];
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = static_lds_matches(p.k1);
+    if (rc || (rc = static_lds_matches(p.k2)) || (rc = static_lds_matches(p.k3))) return rc;
+    out->rows = ladder_kernel(p.k1, p.ladder.row_e, 0, std::max(p.k1.lds_static, p.k3.lds_static));
+    out->cols = ladder_kernel(p.k2, p.ladder.col_e, p.ladder.cw, p.k2.lds_static);
     return FPM_OK;
 }
 

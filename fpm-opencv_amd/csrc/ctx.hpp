@@ -71,6 +71,7 @@ struct fpm_ctx {
     fpm_problem prob{};
     std::vector<int32_t> order, x0, y0;
     int device = 0;
+    size_t lds_limit = 0;           // LDS a workgroup of the device can have (check_device)
     fpm::Switches sw{};             // the environment at fpm_create
     // ---- the plan
     fpm::DevState st{};

@@ -52,6 +52,11 @@ namespace fpm {
 // ---- K1 ---------------------------------------------------------------------
 // grid (nb, B), block 256, LDS 2*Np float2.  Here and in K2, every generation:
 // A = ResArgs adds the grid's z, the LED of the sweep's batch.
+// kLds...: the kernel's own __shared__ bytes, which a launch needs on top of
+// its dynamic LDS (plan_context checks the sum against the device's limit).
+// A static_assert ties each to the array it counts, and fpm_debug_get_ladder
+// compares them with what the compiled kernels report (tests/test_gpu_ladder.py).
+constexpr size_t kLdsGatherRowifft = 0;
 template <class A>
 __global__ void __launch_bounds__(256) k_gather_rowifft(DevState st, A a, FftPlan pl,
                                                         const float2 *__restrict__ tw) {
@@ -84,6 +89,8 @@ __global__ void __launch_bounds__(256) k_gather_rowifft(DevState st, A a, FftPla
 
 // ---- K2 ---------------------------------------------------------------------
 // grid (Np, B), block 256, LDS 2*Np float2. One column per block.
+template <class A>
+constexpr size_t kLdsColpass = kIsRes<A> ? kResPartialLds<4> : 0;  // res_block_partial
 template <class A>
 __global__ void __launch_bounds__(256) k_colpass(DevState st, A a, FftPlan pl,
                                                  const float2 *__restrict__ tw) {
@@ -135,6 +142,7 @@ __global__ void __launch_bounds__(256) k_colpass(DevState st, A a, FftPlan pl,
 
 // ---- K3 ---------------------------------------------------------------------
 // grid (nb, B), block 256, LDS 2*Np float2
+constexpr size_t kLdsRowfftUpdate = 4 * sizeof(float);  // red
 __global__ void __launch_bounds__(256) k_rowfft_update(DevState st, StepArgs sa, FftPlan pl,
                                                        const float2 *__restrict__ tw) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
@@ -151,6 +159,7 @@ __global__ void __launch_bounds__(256) k_rowfft_update(DevState st, StepArgs sa,
     // max|P| of the previous commit: the block reads the npart partial maxima
     // in parallel (a serial scalar-load chain cost ~30 us at npart ~ 100)
     __shared__ float red[4];
+    static_assert(sizeof red == kLdsRowfftUpdate, "the create-time LDS check counts this array");
     float pm = 0.f;
     for (int i = threadIdx.x; i < st.npart; i += blockDim.x) pm = fmaxf(pm, st.pmax[b * st.npart + i]);
     pm = block_max_nonneg(pm, red);
@@ -299,6 +308,9 @@ int pupil_parts(int nb) { return std::max(1, (nb * nb + kCommitPx - 1) / kCommit
 // the twiddles beside it: the row transforms of a block run together, in
 // place, instead of one 256-thread block per row with global twiddle reads.
 // grid (ceil(nb / C), B), block NT.
+constexpr size_t kLdsGatherRowifftTiled = 0;
+template <int NT>
+constexpr size_t kLdsRowfftUpdateTiled = NT / 64 * sizeof(float);  // red
 template <int NT, int E, class A>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16 ? 4 : 1))) k_gather_rowifft_tiled(DevState st, A a, FftPlan pl,
                                                              const float2 *__restrict__ tw, int lc) {
@@ -335,6 +347,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
                                                             const float2 *__restrict__ tw, int lc) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     __shared__ float red[NT / 64];
+    static_assert(sizeof red == kLdsRowfftUpdateTiled<NT>, "the create-time LDS check counts this array");
     const int np = st.np, r = st.r, nb = st.nb, C = 1 << lc, lss = row_pitch(np, lc);
     const int j0 = blockIdx.x << lc, b = blockIdx.y;
     const int cs = min(C, nb - j0);
@@ -376,6 +389,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
 // C: its missing columns are zero and never stored).  grid (ceil(Np / C), B),
 // block NT (256 when the tile fits its register-lifted passes, so a 16 x 200
 // tile keeps every wave busy instead of idling half of a 512-thread block).
+template <int NT, class A>
+constexpr size_t kLdsColpassTiled = kIsRes<A> ? kResPartialLds<NT / 64> : 0;  // res_block_partial
 template <int NT, int E, class A>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16 ? 4 : 1))) k_colpass_tiled(DevState st, A a, FftPlan pl,
                                                       const float2 *__restrict__ tw, int lc) {
@@ -449,6 +464,8 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
 // (rows lane + 64q of its wave's columns) are loaded into registers before
 // the inverse transform, so their latency hides behind it.
 // grid (ceil(Np / (NW*CW)), B), block 64*NW, LDS (NW*CW*pitch + Np) float2
+template <int NW, class A>
+constexpr size_t kLdsColpassWave = kIsRes<A> ? kResPartialLds<NW> : 0;  // res_block_partial
 template <int NW, int CW, class A>
 __global__ void __launch_bounds__(64 * NW)
 k_colpass_wave(DevState st, A a, FftPlan pl, const float2 *__restrict__ tw, int P) {
@@ -550,10 +567,11 @@ k_colpass_wave(DevState st, A a, FftPlan pl, const float2 *__restrict__ tw, int 
 // decided here for the update step and for the residual sweep alike.
 // step: the update step, which trades tile size for block count when a few
 // large patches would leave the chip short of blocks (the sweep gets its
-// blocks from the batch, and alone honours FPM_RES_ONE_SEQ).
+// blocks from the batch).  FPM_ONE_SEQ forces the one-sequence kernels on the
+// step, FPM_RES_ONE_SEQ on the sweep.
 LdsLadder plan_lds_ladder(const FftPlan &pl, int np, int nb, int B, const Switches &sw, bool step) {
     LdsLadder l{};
-    const bool one_seq = !step && sw.res_one_seq;  // the fallback of sizes where not even two fit, at any size
+    const bool one_seq = step ? sw.one_seq : sw.res_one_seq;  // the fallback of sizes where not even two fit, at any size
     const size_t lds = 2 * (size_t)np * sizeof(float2);  // of the one-sequence kernels
     // row kernels: up to 16 box rows per block (one row per block when not
     // even 2 rows fit a 256-thread tile)
@@ -603,17 +621,23 @@ static void pick_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &c
     rows.fn = l.row_e == 16 ? (const void *)k_gather_rowifft_tiled<256, 16, A>
               : l.row_e     ? (const void *)k_gather_rowifft_tiled<256, 24, A>
                             : (const void *)k_gather_rowifft<A>;
+    rows.lds_static = l.row_e ? kLdsGatherRowifftTiled : kLdsGatherRowifft;
     cols = l.cols;
     const bool e16 = l.col_e == 16;
-    if (l.cw)
+    if (l.cw) {
         cols.fn = l.cw == 4 ? (const void *)k_colpass_wave<4, 4, A> : (const void *)k_colpass_wave<4, 2, A>;
-    else if (!l.col_e)
+        cols.lds_static = kLdsColpassWave<4, A>;
+    } else if (!l.col_e) {
         cols.fn = (const void *)k_colpass<A>;
-    else if (cols.block.x == 256)
+        cols.lds_static = kLdsColpass<A>;
+    } else if (cols.block.x == 256) {
         cols.fn = e16 ? (const void *)k_colpass_tiled<256, 16, A> : (const void *)k_colpass_tiled<256, 24, A>;
-    else
+        cols.lds_static = kLdsColpassTiled<256, A>;
+    } else {
         cols.fn = e16 ? (const void *)k_colpass_tiled<kFftThreads, 16, A>
                       : (const void *)k_colpass_tiled<kFftThreads, 24, A>;
+        cols.lds_static = kLdsColpassTiled<kFftThreads, A>;
+    }
 }
 
 GeneralPlan plan_general_step(const DevState &st, GeneralPlan::Kind kind, const FftPlan &pl, const Switches &sw) {
@@ -625,11 +649,13 @@ GeneralPlan plan_general_step(const DevState &st, GeneralPlan::Kind kind, const 
     p.kind = kind;
     if (p.kind != GeneralPlan::Lds) return p;
     const LdsLadder l = plan_lds_ladder(pl, st.np, st.nb, st.B, sw, true);
+    p.ladder = l;
     pick_lds_kernels<StepArgs>(l, p.k1, p.k2);
     p.k3 = l.rows;
     p.k3.fn = l.row_e == 16 ? (const void *)k_rowfft_update_tiled<256, 16>
               : l.row_e     ? (const void *)k_rowfft_update_tiled<256, 24>
                             : (const void *)k_rowfft_update;
+    p.k3.lds_static = l.row_e ? kLdsRowfftUpdateTiled<256> : kLdsRowfftUpdate;
     return p;
 }
 
@@ -649,9 +675,11 @@ hipError_t launch_general_step(const GeneralPlan &plan, const DevState &st, int 
     } else if (plan.kind == GeneralPlan::Reg256) {
         return launch_np256_rows_cols(st, sa, tw, !first, s);  // K4 inside, K5 folded
     } else {
-        (void)launch_step_kernel(plan.k1, st, sa, plan.pl, tw, s);
-        (void)launch_step_kernel(plan.k2, st, sa, plan.pl, tw, s);
-        (void)launch_step_kernel(plan.k3, st, sa, plan.pl, tw, s);
+        // a refused launch would leave T stale under K4 / K5: the first error ends the step
+        for (const StepKernel *k : {&plan.k1, &plan.k2, &plan.k3}) {
+            const hipError_t e = launch_step_kernel(*k, st, sa, plan.pl, tw, s);
+            if (e != hipSuccess) return e;
+        }
     }
     // K4's block size follows the LED's ROI tile columns
     const int nrow = (sa.yc + st.r) / kTile - (sa.yc - st.r) / kTile + 1;

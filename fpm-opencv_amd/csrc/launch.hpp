@@ -6,6 +6,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
+
 #include "fft_lds.hpp"
 #include "fpm_state.hpp"
 #include "fused_host.hpp"
@@ -24,6 +26,7 @@ struct Switches {
     bool res_lds;                             // FPM_RES_LDS: the residual's LDS kernel pair where the register pair applies
     bool res_one_seq;                         // FPM_RES_ONE_SEQ: the LDS pair's one-sequence-per-block kernels at any size
     int res_batch;                            // FPM_RES_BATCH: LEDs per residual launch (> 0), else from the scratch cap
+    bool one_seq;                             // FPM_ONE_SEQ: the update step's one-sequence-per-block kernels at any size
 };
 
 // ---- general path: the LED step (general.hip)
@@ -34,6 +37,8 @@ struct StepKernel {
     dim3 grid, block;
     size_t lds;  // dynamic LDS bytes
     int arg;     // rows per block lr, columns per block lc (both log2) or the column pitch P
+    size_t lds_static;  // the kernel's own __shared__ bytes (the constants beside the kernels, general.hip)
+    size_t lds_total() const { return lds + lds_static; }
 };
 // One launch of an LDS step kernel for the update step (A = StepArgs) or for
 // nl LEDs of the residual sweep (ResArgs: blockIdx.z is the LED of the batch)
@@ -43,6 +48,20 @@ inline hipError_t launch_step_kernel(const StepKernel &k, DevState st, A a, FftP
     int arg = k.arg;
     void *args[] = {&st, &a, &pl, &tw, &arg};  // the one-sequence kernels take the first four
     return hipLaunchKernel(k.fn, dim3(k.grid.x, k.grid.y, nl), k.block, args, k.lds, s);
+}
+// Once per context, before the first launch: a kernel that asks for more than
+// the 64 KB of dynamic LDS a launch may take by default is allowed all the
+// device offers (lds_limit less the kernel's own).  Never this context's own
+// byte count: the attribute belongs to the kernel, and a later context with a
+// smaller tile must not lower it under a live one that needs more.
+inline hipError_t allow_large_lds(std::initializer_list<const StepKernel *> ks, size_t lds_limit) {
+    for (const StepKernel *k : ks)
+        if (k->lds > 64 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(k->fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     (int)(lds_limit - k->lds_static));
+            if (e != hipSuccess) return e;
+        }
+    return hipSuccess;
 }
 // Which generation of the LDS row (K1 / K3) and column (K2) kernels a size
 // runs, and their launch shapes (plan_lds_ladder, general.hip)
@@ -62,6 +81,7 @@ struct GeneralPlan {
     enum Kind { Reg1024, Reg256, Lds } kind;
     FftPlan pl;                               // of Np
     StepKernel k1, k2, k3;                    // Lds only
+    LdsLadder ladder;                         // Lds only: the rung k1-k3 were picked from
     // the register row / column kernels fold the pupil commit into the next
     // LED's row IDFT (launch_pupil_commit after the iteration's last LED)
     bool commit_folded() const { return kind != Lds; }
@@ -105,6 +125,7 @@ struct ResidualPlan {
     enum Kind { Reg256, Lds } kind;
     FftPlan pl;                // of Np
     StepKernel rows, cols;     // one LED's grid: the launch multiplies it by the batch
+    LdsLadder ladder;          // Lds only: the rung rows / cols were picked from
     int nblk;                  // column blocks = partials per (LED, patch)
     int nl;                    // LEDs per launch
     size_t t_led;              // complex elements of T per LED
@@ -115,7 +136,6 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
 // K1 / K2 (general.hip) and the Np 256 register column kernel (np256.hip)
 void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols);
 const void *residual_cols256_kernel();
-hipError_t prepare_residual(const ResidualPlan &p);
 // rows, columns and fold of the nl LEDs at order[ra.i0 ...]
 hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, const ResArgs &ra, int nl,
                                  const float2 *tw, hipStream_t s);

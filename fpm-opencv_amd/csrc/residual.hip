@@ -131,7 +131,8 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
         p.cols = StepKernel{residual_cols256_kernel(), dim3(kColBlocks * Bp), dim3(NT), lds_cols(nb), 0};
         p.nblk = kColBlocks;
     } else {
-        residual_lds_kernels(plan_lds_ladder(pl, np, nb, B, sw, false), p.rows, p.cols);
+        p.ladder = plan_lds_ladder(pl, np, nb, B, sw, false);
+        residual_lds_kernels(p.ladder, p.rows, p.cols);
         p.nblk = (int)p.cols.grid.x;
     }
     // LEDs per launch: as many as the scratch cap holds (FPM_RES_BATCH=n forces n)
@@ -140,16 +141,6 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
     p.nl = sw.res_batch > 0 ? sw.res_batch : (int)std::min<size_t>(std::max<size_t>(fit, 1), 65535);
     p.nl = std::max(1, std::min({p.nl, n_order, 65535}));
     return p;
-}
-
-hipError_t prepare_residual(const ResidualPlan &p) {
-    // beyond the 64 KB a launch may take by default (Np 1024 and up, tiled columns)
-    for (const StepKernel *k : {&p.rows, &p.cols})
-        if (k->lds > 64 * 1024) {
-            const hipError_t e = hipFuncSetAttribute(k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)k->lds);
-            if (e != hipSuccess) return e;
-        }
-    return hipSuccess;
 }
 
 hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, const ResArgs &ra_in, int nl,

@@ -32,7 +32,7 @@ int ensure_scratch(fpm_ctx *c) {
     if (rc) return rc;
     for (auto &e : c->res_ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(prepare_residual(p));
+    HIP_TRY(allow_large_lds({&p.rows, &p.cols}, c->lds_limit));  // Np 1024 and up, tiled columns
     c->res_ready = true;
     return FPM_OK;
 }

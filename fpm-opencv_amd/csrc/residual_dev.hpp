@@ -53,11 +53,14 @@ __device__ __forceinline__ float2 *res_T(const DevState &st, const ResArgs &ra, 
 
 // The block's sums as one partial: lanes -> wave in double / u64 (xor
 // butterfly, a fixed association), waves -> block in wave order by thread 0.
-// Every thread of the block must call it.
+// Every thread of the block must call it.  kResPartialLds: its __shared__ bytes.
+template <int NW>
+constexpr size_t kResPartialLds = NW * (sizeof(double) + sizeof(unsigned long long));
 template <int NW>
 __device__ __forceinline__ void res_block_partial(float acc, unsigned isum, const ResArgs &ra, size_t slot) {
     __shared__ double dred[NW];
     __shared__ unsigned long long ured[NW];
+    static_assert(sizeof dred + sizeof ured == kResPartialLds<NW>, "the create-time LDS check counts these arrays");
     double d = (double)acc;
     unsigned long long u = isum;
 #pragma unroll

@@ -53,7 +53,9 @@ HIP_SYMBOLS = (
 )
 # test-only entry points (include/fpm_hip_debug.h)
 HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan",
-                     "fpm_debug_get_maxima")
+                     "fpm_debug_get_maxima", "fpm_debug_plan_ladder", "fpm_debug_get_ladder")
+# fpm_ladder_kernel.generation
+LADDER_ONE_SEQ, LADDER_TILED, LADDER_WAVE = 0, 1, 2
 # fpm_debug_get_plan: general_kind / residual_kind values
 GENERAL_REG1024, GENERAL_REG256, GENERAL_LDS = 0, 1, 2
 RESIDUAL_REG256, RESIDUAL_LDS = 0, 1
@@ -104,6 +106,21 @@ class fpm_clock(C.Structure):
                 ("ms_per_launch", C.c_double), ("launches", C.c_int32)]
 
 
+class fpm_ladder_kernel(C.Structure):
+    _fields_ = [("generation", C.c_int), ("tile", C.c_int), ("threads", C.c_int), ("e", C.c_int),
+                ("grid_x", C.c_int), ("grid_y", C.c_int), ("lds_dynamic", C.c_int), ("lds_static", C.c_int)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
+class fpm_ladder(C.Structure):
+    _fields_ = [("rows", fpm_ladder_kernel), ("cols", fpm_ladder_kernel)]
+
+    def as_dict(self):
+        return dict(rows=self.rows.as_dict(), cols=self.cols.as_dict())
+
+
 _lib = None
 
 
@@ -136,6 +153,8 @@ def load_library(path: str = HIP_LIB):
         "fpm_debug_set_stall": (C.c_int, [vp, C.c_int]),
         "fpm_debug_get_plan": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "fpm_debug_get_maxima": (C.c_int, [vp, C.POINTER(C.c_int), f32p, C.POINTER(C.c_uint8), f32p, f32p]),
+        "fpm_debug_plan_ladder": (C.c_int, [C.c_int] * 6 + [C.POINTER(fpm_ladder)]),
+        "fpm_debug_get_ladder": (C.c_int, [vp, C.c_int, C.POINTER(fpm_ladder)]),
         "fpm_get_timing": (C.c_int, [vp, C.POINTER(fpm_timing)]),
         "fpm_get_clock": (C.c_int, [vp, C.POINTER(fpm_clock)]),
         "fpm_residual": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -357,6 +376,14 @@ class Solver:
                                          _f32p(rmax), _f32p(pmax)))
         return dict(tmax=tmax, dirty=dirty.astype(bool), rmax=rmax, pmax=pmax)
 
+    def debug_ladder(self, residual: bool = False) -> dict:
+        """Test-only (include/fpm_hip_debug.h): the rung of the LDS kernel ladder
+        the context's update step (or, residual=True, its sweep) launches, as
+        debug_plan_ladder returns it."""
+        l = fpm_ladder()
+        _check(_lib.fpm_debug_get_ladder(self._h, int(residual), C.byref(l)))
+        return l.as_dict()
+
     def timing(self) -> fpm_timing:
         t = fpm_timing()
         _check(_lib.fpm_get_timing(self._h, C.byref(t)))
@@ -368,6 +395,19 @@ class Solver:
         k = fpm_clock()
         _check(_lib.fpm_get_clock(self._h, C.byref(k)))
         return k
+
+
+def debug_plan_ladder(np_: int, nb: int, B: int, step: bool = True, no_wave_cols: bool = False,
+                      one_seq: bool = False) -> dict:
+    """Test-only (include/fpm_hip_debug.h): what the general path's planner
+    picks for (Np, nb, B): {"rows": ..., "cols": ...}, each with generation
+    (LADDER_*), tile, threads, e, grid_x, grid_y, lds_dynamic, lds_static.
+    Needs no GPU."""
+    lib = load_library()
+    l = fpm_ladder()
+    _check(lib.fpm_debug_plan_ladder(int(np_), int(nb), int(B), int(step), int(no_wave_cols), int(one_seq),
+                                     C.byref(l)))
+    return l.as_dict()
 
 
 def normalised_residual(d) -> np.ndarray:

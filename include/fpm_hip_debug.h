@@ -57,6 +57,41 @@ int fpm_debug_get_plan(const fpm_ctx *ctx, int *meas_g, int *general_kind, int *
  *   pmax  [B][npart]    partial maxima of |P| */
 int fpm_debug_get_maxima(const fpm_ctx *ctx, int *dims, float *tmax, unsigned char *dirty, float *rmax, float *pmax);
 
+/* The rung of the general path's LDS kernel ladder (general.hip: one sequence
+ * per block, row / column tiles, wave-private columns) that a size runs, as
+ * plan_lds_ladder and pick_lds_kernels decide it, for the row kernels (K1, and
+ * K3 in the update step) and the column kernel (K2). */
+#define FPM_LADDER_ONE_SEQ 0
+#define FPM_LADDER_TILED 1
+#define FPM_LADDER_WAVE 2
+typedef struct fpm_ladder_kernel {
+    int generation;  /* FPM_LADDER_* */
+    int tile;        /* tiled: log2 of the rows (lr) / columns (lc) per block; wave: columns per wave (cw); else 0 */
+    int threads;     /* per block */
+    int e;           /* register elements per thread: tiled 16 / 24, wave 16, one sequence per block 0 */
+    int grid_x, grid_y;
+    int lds_dynamic; /* bytes the launch asks for */
+    int lds_static;  /* bytes of the kernel's own __shared__ arrays (rows of the update step: the larger of K1's and K3's) */
+} fpm_ladder_kernel;
+typedef struct fpm_ladder {
+    fpm_ladder_kernel rows, cols;
+} fpm_ladder;
+
+/* The rung for box size nb = 2r+1 and B patches at Np = np, of the update step
+ * (step = 1) or of the residual sweep (step = 0); no_wave_cols and one_seq are
+ * the switches FPM_NO_WAVE_COLS and FPM_ONE_SEQ (step) / FPM_RES_ONE_SEQ
+ * (sweep).  Calls the planner itself and nothing of HIP: needs neither a
+ * context nor a device.  FPM_ERR_INVAL when np is not 2^a 3^b 5^c. */
+int fpm_debug_plan_ladder(int np, int nb, int B, int step, int no_wave_cols, int one_seq, fpm_ladder *out);
+
+/* The same record of a live context on the general path's LDS kernels: what its
+ * update step (residual = 0; patch group 0) or its residual sweep (residual = 1)
+ * launches.  FPM_ERR_INVAL on a fused context and on one whose step runs the
+ * register kernels (Np 1024, Np 256).  Also compares each launched kernel's
+ * static LDS constant with what its compiled code declares: FPM_ERR_STATE if
+ * they differ. */
+int fpm_debug_get_ladder(const fpm_ctx *ctx, int residual, fpm_ladder *out);
+
 #ifdef __cplusplus
 }
 #endif

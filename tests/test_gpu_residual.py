@@ -33,6 +33,7 @@ import numpy as np
 import pytest
 
 import fpm_amd
+import residual_check
 from tools.synth import grid_geometry, make_stack
 
 pytestmark = pytest.mark.gpu
@@ -91,37 +92,8 @@ def _solver(prob, stack, iters, kernels, plan=None, **env):
         s.close()
 
 
-def _reference(state, stack, prob):
-    """float64 E, Q [n_order][B] and the integer S of the downloaded state."""
-    Np, B = prob.np_, prob.n_patch
-    n = len(prob.order)
-    E, Q, S = np.empty((n, B)), np.empty((n, B)), np.empty((n, B))
-    for b in range(B):
-        O = np.fft.fftshift(state["objF"][b].astype(np.complex128))
-        P = np.fft.ifftshift(state["pupil"][b].astype(np.complex128))
-        for i, led in enumerate(prob.order):
-            xs, ys = int(prob.x0[led]), int(prob.y0[led])
-            a = np.abs(np.fft.ifft2(np.fft.ifftshift(O[ys:ys + Np, xs:xs + Np]) * P))
-            I = stack[led, b].astype(np.float64)
-            E[i, b] = ((a - np.sqrt(I)) ** 2).sum()
-            Q[i, b] = (a * a).sum()
-            S[i, b] = float(stack[led, b].astype(np.int64).sum())
-    return E, Q, S
-
-
-def _bound(E, Q):
-    return 2e-5 * np.sqrt(E * Q) + 1e-10 * Q
-
-
-def _check(tag, d, ref):
-    E, Q, S = ref
-    delta, bound = np.abs(d["err"] - E), _bound(E, Q)
-    # a window that misses the spectrum's support for good has psi = 0: Q = 0, the bound is 0 and E = S exactly
-    ratio = np.divide(delta, bound, out=np.zeros_like(delta), where=bound > 0)
-    print(f"residual {tag}: max |dE|/bound {ratio.max():.3e}  ({int((bound == 0).sum())} of {bound.size} with Q = 0; "
-          f"E/S {d['err'].sum() / S.sum():.3e}, sweep {d['ms']:.3f} ms)")
-    assert np.all(np.isfinite(d["err"])) and np.all(delta <= bound), (tag, float(ratio.max()), float(delta.max()))
-    np.testing.assert_array_equal(d["ref"], S)
+# the float64 yardstick, its bound and the comparison: shared with tests/test_gpu_ladder.py
+_reference, _bound, _check = residual_check.reference, residual_check.bound, residual_check.check
 
 
 def _parity(tag, prob, stack, iters, kernels, plan, **env):
