@@ -2,12 +2,15 @@
 // device, plan the context (plan_context: every decision, no HIP call), then
 // allocate what the plan names and upload the tables.  The context owns what
 // it created: its destructor releases it, on fpm_destroy and on every failed
-// fpm_create alike.
+// fpm_create alike.  fpm_set_crops replaces the crop table of a live context:
+// it plans the new table the same way and takes it only if the plan is the
+// live one's.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <string>
 
 #include "../../include/fpm_hip_debug.h"
 #include "ctx.hpp"
@@ -95,6 +98,15 @@ std::vector<float2> twiddles(int n) {
     return t;
 }
 
+// cv::Rect(cropXStart, cropYStart, Np, Np) must lie inside objF (fpmMain.cpp:361)
+int validate_crops(int np, int nlarge, int n_stack, const int32_t *x0, const int32_t *y0) {
+    for (int i = 0; i < n_stack; ++i)
+        if (x0[i] < 0 || x0[i] > nlarge - np || y0[i] < 0 || y0[i] > nlarge - np)
+            return set_err(FPM_ERR_INVAL, "LED %d crop (%d,%d) leaves the %dx%d spectrum", i, x0[i], y0[i], nlarge,
+                           nlarge);
+    return FPM_OK;
+}
+
 int validate(const fpm_problem *p) {
     if (!p) return set_err(FPM_ERR_INVAL, "null problem");
     if (p->np < 4 || (p->np & 1)) return set_err(FPM_ERR_INVAL, "Np=%d must be even and >= 4", p->np);
@@ -119,14 +131,7 @@ int validate(const fpm_problem *p) {
     for (int i = 0; i < p->n_order; ++i)
         if (p->order[i] < 0 || p->order[i] >= p->n_stack)
             return set_err(FPM_ERR_INVAL, "order[%d]=%d outside the stack", i, p->order[i]);
-    for (int i = 0; i < p->n_stack; ++i) {
-        // cv::Rect(cropXStart, cropYStart, Np, Np) must lie inside objF (fpmMain.cpp:361)
-        if (p->crop_x0[i] < 0 || p->crop_x0[i] > p->nlarge - p->np || p->crop_y0[i] < 0 ||
-            p->crop_y0[i] > p->nlarge - p->np)
-            return set_err(FPM_ERR_INVAL, "LED %d crop (%d,%d) leaves the %dx%d spectrum", i, p->crop_x0[i],
-                           p->crop_y0[i], p->nlarge, p->nlarge);
-    }
-    return FPM_OK;
+    return validate_crops(p->np, p->nlarge, p->n_stack, p->crop_x0, p->crop_y0);
 }
 
 // a gfx950 device; makes it current and reports its CU count and the LDS a
@@ -146,8 +151,9 @@ int check_device(int device, int *n_cu, size_t *lds_limit) {
     return FPM_OK;
 }
 
-// the DevState scalars of the validated problem c->prob
-void plan_state(fpm_ctx *c) {
+// the DevState scalars of the validated problem c->prob; keep: a live
+// context's state whose band the new one must contain (fpm_set_crops)
+void plan_state(fpm_ctx *c, const DevState *keep) {
     const fpm_problem &p = c->prob;
     const int np = p.np, L = p.nlarge, r = p.na_radius;
     DevState &st = c->st;
@@ -185,6 +191,14 @@ void plan_state(fpm_ctx *c) {
     st.sx0 = std::max(st.sx0, 0);
     st.sy1 = std::min(st.sy1, L - 1);
     st.sx1 = std::min(st.sx1, L - 1);
+    // never shrunk: what earlier LEDs wrote stays inside the band that objCrop
+    // and the maxima scans read
+    if (keep) {
+        st.sy0 = std::min(st.sy0, keep->sy0);
+        st.sx0 = std::min(st.sx0, keep->sx0);
+        st.sy1 = std::max(st.sy1, keep->sy1);
+        st.sx1 = std::max(st.sx1, keep->sx1);
+    }
 }
 
 // a planned launch within the LDS a workgroup can have (dynamic plus the kernel's own)
@@ -208,12 +222,12 @@ int residual_lds_fits(const fpm_ctx *c, size_t lds_limit) {
 // Refuses a fused path that this geometry or fp16 spectrum storage does not
 // have, and a size whose planned step or sweep kernel needs more LDS than the
 // device offers (Np 10240: DESIGN.md section 4.7).
-int plan_context(fpm_ctx *c, int n_cu, size_t lds_limit) {
+int plan_context(fpm_ctx *c, int n_cu, size_t lds_limit, const DevState *keep = nullptr) {
     const fpm_problem &p = c->prob;
     const Switches &sw = c->sw;
     const int np = p.np, L = p.nlarge, r = p.na_radius, nb = 2 * r + 1, B = p.n_patch;
     DevState &st = c->st;
-    plan_state(c);
+    plan_state(c, keep);
     make_plan(np, &c->pl_np);
     make_plan(L, &c->pl_L);
 
@@ -316,6 +330,7 @@ int allocate(fpm_ctx *c) {
     get(&c->order_dev, c->order.size());
     get(&c->x0_dev, c->x0.size());
     get(&c->y0_dev, c->y0.size());
+    get(&c->ident_dev, c->order.size());
     if (c->fused()) {
         get(&st.T, fused_T_elems(st.np, st.r, st.B));
         if (c->split_ks > 1) {
@@ -353,14 +368,74 @@ int allocate(fpm_ctx *c) {
     return FPM_OK;
 }
 
+template <class V>
+bool put(void *dst, const V &v) {
+    return hipMemcpy(dst, v.data(), v.size() * sizeof v[0], hipMemcpyHostToDevice) == hipSuccess;
+}
+
+// the crop table and what is derived from it: fpm_residual's entry list
+bool upload_crops(fpm_ctx *c) {
+    std::vector<ResEntry> ident(c->order.size());
+    for (size_t i = 0; i < ident.size(); ++i) {
+        const int led = c->order[i];
+        ident[i] = ResEntry{led, c->x0[led] + c->st.np / 2, c->y0[led] + c->st.np / 2, 0};
+    }
+    return put(c->x0_dev, c->x0) && put(c->y0_dev, c->y0) && put(c->ident_dev, ident);
+}
+
 int upload_tables(fpm_ctx *c) {
     const auto twn = twiddles(c->st.np), twl = twiddles(c->st.L);
-    auto put = [](void *dst, const auto &v) {
-        return hipMemcpy(dst, v.data(), v.size() * sizeof v[0], hipMemcpyHostToDevice) == hipSuccess;
-    };
     if (!put(c->tw_np, twn) || !put(c->tw_L, twl) || !put(c->disk_dev, c->disk) || !put(c->order_dev, c->order) ||
-        !put(c->x0_dev, c->x0) || !put(c->y0_dev, c->y0))
+        !upload_crops(c))
         return set_err(FPM_ERR_DEVICE, "table upload failed");
+    return FPM_OK;
+}
+
+// ---- fpm_set_crops: is the new table's plan the live context's? ---------------------
+bool same_kernel(const StepKernel &a, const StepKernel &b) {
+    return a.fn == b.fn && a.grid.x == b.grid.x && a.grid.y == b.grid.y && a.grid.z == b.grid.z &&
+           a.block.x == b.block.x && a.lds == b.lds && a.arg == b.arg && a.lds_static == b.lds_static;
+}
+
+// the first difference between two plans by name, or null: everything
+// plan_context decides that a launch or an allocation of the live context relies on
+const char *plan_difference(const fpm_ctx *a, const fpm_ctx *b) {
+    if (a->kernel != b->kernel) return "the LED-update kernel";
+    if (a->split_ks != b->split_ks) return "the workgroups per patch";
+    if (a->general_kind != b->general_kind || a->t16 != b->t16) return "the general path's step kernels";
+    if (a->meas_g != b->meas_g) return "the stack's device layout";
+    if (a->ngroups != b->ngroups) return "the patch groups";
+    if (a->st.npart != b->st.npart) return "the pupil-maximum partials";
+    const ResidualPlan &p = a->rplan, &q = b->rplan;
+    if (p.kind != q.kind || p.nblk != q.nblk || p.nl != q.nl || p.t_led != q.t_led || !same_kernel(p.rows, q.rows) ||
+        !same_kernel(p.cols, q.cols))
+        return "the residual sweep's plan";
+    for (int g = 0; !a->fused() && g < a->ngroups; ++g) {
+        const GeneralPlan &u = a->gplan[g], &v = b->gplan[g];
+        if (u.kind != v.kind || (u.kind == GeneralPlan::Lds && (!same_kernel(u.k1, v.k1) || !same_kernel(u.k2, v.k2) ||
+                                                                 !same_kernel(u.k3, v.k3))))
+            return "the general path's step plan";
+    }
+    return nullptr;
+}
+
+// The fused kernels keep a patch's dirty bits indexed by band tile
+// (tilemax.hpp): bit k is tile (bty0 + k / nbx, btx0 + k % nbx).  A band that
+// grew renumbers them; tiles newly inside it are clean, and their tmax is the
+// 0 fpm_init wrote (the spectrum is zero there).  The stream is idle.
+int remap_dirty_bits(fpm_ctx *c, const BandArgs &from, const BandArgs &to) {
+    const DevState &st = c->st;
+    const size_t nw = ((size_t)st.ntx * st.nty + 31) / 32;
+    std::vector<unsigned> old_bits(st.B * nw), bits(st.B * nw, 0u);
+    HIP_TRY(hipMemcpy(old_bits.data(), st.tdirty, old_bits.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < (size_t)st.B; ++b)
+        for (int k = 0; k < from.nbt; ++k)
+            if ((old_bits[b * nw + (k >> 5)] >> (k & 31)) & 1u) {
+                const int ty = from.bty0 + k / from.nbx, tx = from.btx0 + k % from.nbx;
+                const int j = (ty - to.bty0) * to.nbx + (tx - to.btx0);
+                bits[b * nw + (j >> 5)] |= 1u << (j & 31);
+            }
+    HIP_TRY(hipMemcpy(st.tdirty, bits.data(), bits.size() * sizeof(unsigned), hipMemcpyHostToDevice));
     return FPM_OK;
 }
 
@@ -379,6 +454,7 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
     c->prob = *prob;
     c->device = device;
     c->lds_limit = lds_limit;
+    c->n_cu = n_cu;
     c->sw = read_switches();
     c->order.assign(prob->order, prob->order + prob->n_order);
     c->x0.assign(prob->crop_x0, prob->crop_x0 + prob->n_stack);
@@ -401,6 +477,56 @@ void fpm_destroy(fpm_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     delete c;
+}
+
+int fpm_get_crops(const fpm_ctx *c, int32_t *crop_x0, int32_t *crop_y0) {
+    if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
+    if (crop_x0) std::copy(c->x0.begin(), c->x0.end(), crop_x0);
+    if (crop_y0) std::copy(c->y0.begin(), c->y0.end(), crop_y0);
+    return FPM_OK;
+}
+
+int fpm_set_crops(fpm_ctx *c, const int32_t *crop_x0, const int32_t *crop_y0) {
+    if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
+    if (!crop_x0 || !crop_y0) return set_err(FPM_ERR_INVAL, "fpm_set_crops: null crop arrays");
+    const fpm_problem &p = c->prob;
+    int rc = validate_crops(p.np, p.nlarge, p.n_stack, crop_x0, crop_y0);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if ((rc = refuse_capture(c, "fpm_set_crops"))) return rc;
+    // the new table planned on a scratch context that owns nothing (no HIP
+    // call), its band grown to hold the live one
+    fpm_ctx t;
+    t.prob = c->prob;
+    t.sw = c->sw;
+    t.order = c->order;
+    t.x0.assign(crop_x0, crop_x0 + p.n_stack);
+    t.y0.assign(crop_y0, crop_y0 + p.n_stack);
+    t.prob.order = t.order.data();
+    t.prob.crop_x0 = t.x0.data();
+    t.prob.crop_y0 = t.y0.data();
+    if ((rc = plan_context(&t, c->n_cu, c->lds_limit, &c->st))) {
+        const std::string why = fpm_last_error();
+        return set_err(rc, "fpm_set_crops: the new table does not fit this context (%s)", why.c_str());
+    }
+    if (const char *what = plan_difference(c, &t))
+        return set_err(FPM_ERR_INVAL, "fpm_set_crops: the new table changes %s this context was created with; "
+                       "create a new context for it", what);
+    // nothing in flight reads the tables or the band while they change
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const BandArgs from = band_of(c->st), to = band_of(t.st);
+    const bool renumber = c->fused() && c->initialized &&
+                          (from.bty0 != to.bty0 || from.btx0 != to.btx0 || from.nbx != to.nbx || from.nbt != to.nbt);
+    if (renumber && (rc = remap_dirty_bits(c, from, to))) return rc;
+    std::copy(t.x0.begin(), t.x0.end(), c->x0.begin());  // in place: c->prob points at them
+    std::copy(t.y0.begin(), t.y0.end(), c->y0.begin());
+    c->st.sy0 = t.st.sy0;
+    c->st.sy1 = t.st.sy1;
+    c->st.sx0 = t.st.sx0;
+    c->st.sx1 = t.st.sx1;
+    if (!upload_crops(c)) return set_err(FPM_ERR_DEVICE, "fpm_set_crops: table upload failed");
+    c->drop_graphs();  // the general path's graphs hold the old windows: the next fpm_run captures again
+    return FPM_OK;
 }
 
 int fpm_set_stream(fpm_ctx *c, void *s) {

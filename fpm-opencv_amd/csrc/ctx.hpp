@@ -1,9 +1,9 @@
 // ctx.hpp -- the context behind the extern "C" boundary of libfpm_hip.so
 // (include/fpm_hip.h), shared by the files that implement it:
-//   create.cpp    validate, plan, allocate, destroy
+//   create.cpp    validate, plan, allocate, destroy; fpm_set_crops / fpm_get_crops
 //   transfer.cpp  the stack uploads and the downloads
 //   run.cpp       fpm_init, fpm_run, the general path's patch groups and graphs
-//   residual_api.cpp  fpm_residual (kernels: residual.hip)
+//   residual_api.cpp  fpm_residual, fpm_residual_at (kernels: residual.hip)
 //   api.cpp       errors, version, info, timing, clock, fpm_runFPM
 // Errors are negative codes plus fpm_last_error(); nothing here ever falls
 // back to a CPU path.
@@ -72,6 +72,7 @@ struct fpm_ctx {
     std::vector<int32_t> order, x0, y0;
     int device = 0;
     size_t lds_limit = 0;           // LDS a workgroup of the device can have (check_device)
+    int n_cu = 0;                   // its compute units (check_device): fpm_set_crops plans again with both
     fpm::Switches sw{};             // the environment at fpm_create
     // ---- the plan
     fpm::DevState st{};
@@ -104,6 +105,9 @@ struct fpm_ctx {
     int stall_led = -1;             //   fpm_debug_set_stall (tests): the last part stops publishing
     unsigned dist_tags = 0;         //   distributed mode: LEDs launched so far (tile-word tags)
     int *order_dev = nullptr, *x0_dev = nullptr, *y0_dev = nullptr;
+    // fpm_residual's entry list: (order[i], window centre of order[i]) for every
+    // position i, rebuilt whenever the crop table changes (upload_tables, fpm_set_crops)
+    fpm::ResEntry *ident_dev = nullptr;
     uint8_t *disk_dev = nullptr;
     std::vector<void *> allocs;
     size_t bytes = 0;
@@ -122,9 +126,11 @@ struct fpm_ctx {
     hipEvent_t gfork = nullptr, gjoin[kMaxGroups] = {};
     fpm::GeneralPlan gplan[kMaxGroups] = {};  // what each group's LED step launches (plan_general_step)
 
-    // fpm_residual's scratch, allocated by its first call: T of one batch, the
-    // per-block partials, the folded [n_order][B] sums, and its two events
+    // the residual's scratch, allocated by the first fpm_residual / fpm_residual_at:
+    // T of one batch, the per-block partials, the folded [n_order][B] sums, the
+    // [n_order] entries of one piece of a probe list, and its two events
     float2 *res_T = nullptr;
+    fpm::ResEntry *res_ent = nullptr;
     double *res_perr = nullptr, *res_err = nullptr, *res_ref = nullptr;
     unsigned long long *res_pref = nullptr;
     hipEvent_t res_ev[2] = {};

@@ -108,15 +108,25 @@ hipError_t launch_np256_rows_cols(const DevState &st, const StepArgs &sa, const 
 // 28 000 column blocks, tens of rounds of workgroups: a larger batch adds
 // memory and no parallelism.
 constexpr size_t kResidualScratchBytes = (size_t)256 << 20;
-// What a residual launch reads besides the state: the device copies of
-// order[] and the crop tables, and the context's residual scratch.
+// One entry of a residual launch's list: the image and where its sub-aperture
+// window sits, resolved on the host (order[pos], crop + offset + Np / 2) so a
+// block finds its LED with a single 16-byte load.
+struct alignas(16) ResEntry {
+    int led;     // stack index
+    int xc, yc;  // centre of the window in the centred spectrum
+    int pad;
+};
+static_assert(sizeof(ResEntry) == 16, "res_led reads an entry as one int4");
+// What a residual launch reads besides the state: the entry list (fpm_residual:
+// the context's identity list, one entry per position of order[];
+// fpm_residual_at: the caller's probes) and the context's residual scratch.
 struct ResArgs {
-    const int *order, *x0, *y0;
-    int i0;                    // position in order[] of the batch's first LED
+    const ResEntry *ent;
+    int i0;                    // index in ent[] of the batch's first entry
     float2 *T;                 // [nl][B][nb][Np] row-transform scratch
     double *perr;              // [nl][B][nblk] one partial of E per column block
     unsigned long long *pref;  //                and of S
-    double *err, *ref;         // [n_order][B] the folded sums
+    double *err, *ref;         // [n][B] the folded sums, by entry index
     int nblk;
 };
 // Which kernel pair a context's sweep launches and how many LEDs at a time;
@@ -136,7 +146,7 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
 // K1 / K2 (general.hip) and the Np 256 register column kernel (np256.hip)
 void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols);
 const void *residual_cols256_kernel();
-// rows, columns and fold of the nl LEDs at order[ra.i0 ...]
+// rows, columns and fold of the nl entries ra.ent[ra.i0 ...]
 hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, const ResArgs &ra, int nl,
                                  const float2 *tw, hipStream_t s);
 

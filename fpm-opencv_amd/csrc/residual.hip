@@ -1,12 +1,14 @@
 // residual.hip -- the data-fidelity residual of the current state
-// (fpm_residual, fpm_hip.h): for the LED at position i of order[]
+// (fpm_residual, fpm_residual_at, fpm_hip.h): for the LED at position i of
+// order[] -- or, for any entry of a list, that LED's image with its window
+// wherever the entry puts it --
 //     E[i] = sum_yx (|psi_i(y,x)| - sqrt(I_i(y,x)))^2,   S[i] = sum_yx I_i
 // with psi_i = ifft2(ifftshift(window_i(O)) P) / Np^2, the reference's
 // ObjcropP (fpmMain.cpp:358-365), evaluated without any update.  This is the
 // first third of an LED step, so its kernels ARE the step's: general.hip's
 // K1 / K2 (every generation) and np256.hip's C are templates over their
 // argument struct, and the sweep launches their ResArgs instances
-// (residual_dev.hpp: the LED from order[], T of the batch, and the sums as
+// (residual_dev.hpp: the LED and its window from the entry list, T of the batch, and the sums as
 // K2's tail in place of amplitude replacement, forward transform and
 // write-back).  Unlike the update loop every LED is independent: one launch
 // covers a batch of nl LEDs x all B patches (blockIdx.z, or the leading factor
@@ -106,7 +108,7 @@ __global__ void __launch_bounds__(256) k_res_fold(ResArgs ra, int nl, int B) {
         e += pe[k];
         s += pr[k];
     }
-    const size_t o = (size_t)ra.i0 * B + i;  // [n_order][B]
+    const size_t o = (size_t)ra.i0 * B + i;  // [n][B], by entry index
     ra.err[o] = e;
     ra.ref[o] = (double)s;  // exact: S < 2^16 Np^2 < 2^53
 }

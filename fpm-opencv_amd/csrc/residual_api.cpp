@@ -1,8 +1,13 @@
-// residual_api.cpp -- fpm_residual: the data-fidelity residual of the current
-// state (residual.hip) as a sequence of steps: refuse a capturing stream,
-// make sure the scratch exists, launch the LED batches between two events,
-// copy the folded sums out, report the event time.  Read-only: nothing of the
-// state, the stack or the last run's timing and clock is written.
+// residual_api.cpp -- fpm_residual and fpm_residual_at: the data-fidelity
+// residual of the current state (residual.hip) as a sequence of steps: refuse
+// a capturing stream, make sure the scratch exists, launch the batches of an
+// entry list between two events, copy the folded sums out, report the event
+// time.  One path: fpm_residual sweeps the context's identity list (every
+// position of order[] with its own window), fpm_residual_at a list the caller
+// gives as (position, offset) probes, resolved and validated on the host and
+// run in pieces of at most n_order entries, the size of the folded-sum scratch.
+// Read-only: nothing of the state, the stack or the last run's timing and
+// clock is written.
 // (The kernels' file is residual.hip; the two cannot share a basename, Makefile.)
 #include <algorithm>
 #include <vector>
@@ -28,6 +33,7 @@ int ensure_scratch(fpm_ctx *c) {
     get(&c->res_pref, part);
     get(&c->res_err, out);
     get(&c->res_ref, out);
+    get(&c->res_ent, (size_t)c->prob.n_order);
     get(&c->res_T, (size_t)p.nl * p.t_led);
     if (rc) return rc;
     for (auto &e : c->res_ev)
@@ -37,28 +43,35 @@ int ensure_scratch(fpm_ctx *c) {
     return FPM_OK;
 }
 
-}  // namespace
-
-extern "C" int fpm_residual(fpm_ctx *c, double *err, double *ref, double *elapsed_ms) {
-    if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
-    if (!err && !ref) return set_err(FPM_ERR_INVAL, "fpm_residual: err and ref are both NULL");
-    if (!c->initialized) return set_err(FPM_ERR_STATE, "fpm_residual before fpm_init");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = refuse_capture(c, "fpm_residual");
-    if (rc || (rc = ensure_scratch(c))) return rc;
+// the entries ent[0, n) (device, n <= n_order) in list order, nl per launch
+int launch_entries(fpm_ctx *c, const ResEntry *ent, int n) {
     const ResidualPlan &p = c->rplan;
-    const int n = c->prob.n_order;
-    ResArgs ra{c->order_dev, c->x0_dev, c->y0_dev, 0, c->res_T, c->res_perr, c->res_pref, c->res_err, c->res_ref,
-               p.nblk};
-    HIP_TRY(hipEventRecord(c->res_ev[0], c->stream));
+    ResArgs ra{ent, 0, c->res_T, c->res_perr, c->res_pref, c->res_err, c->res_ref, p.nblk};
     for (int i0 = 0; i0 < n; i0 += p.nl) {
         ra.i0 = i0;
         HIP_TRY(launch_residual_batch(p, c->st, ra, std::min(p.nl, n - i0), c->tw_np, c->stream));
     }
-    HIP_TRY(hipEventRecord(c->res_ev[1], c->stream));
+    return FPM_OK;
+}
+
+// their folded sums [n][B] to err / ref (either may be null)
+int copy_sums(fpm_ctx *c, int n, double *err, double *ref) {
     const size_t bytes = (size_t)n * c->st.B * sizeof(double);
     if (err) HIP_TRY(hipMemcpyAsync(err, c->res_err, bytes, hipMemcpyDeviceToHost, c->stream));
     if (ref) HIP_TRY(hipMemcpyAsync(ref, c->res_ref, bytes, hipMemcpyDeviceToHost, c->stream));
+    return FPM_OK;
+}
+
+// what both entry points check before anything is enqueued
+int admit(fpm_ctx *c, const char *what, const double *err, const double *ref) {
+    if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
+    if (!err && !ref) return set_err(FPM_ERR_INVAL, "%s: err and ref are both NULL", what);
+    if (!c->initialized) return set_err(FPM_ERR_STATE, "%s before fpm_init", what);
+    HIP_TRY(hipSetDevice(c->device));
+    return refuse_capture(c, what);
+}
+
+int finish(fpm_ctx *c, double *elapsed_ms) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (elapsed_ms) {
         float ms = 0;
@@ -66,4 +79,55 @@ extern "C" int fpm_residual(fpm_ctx *c, double *err, double *ref, double *elapse
         *elapsed_ms = ms;
     }
     return FPM_OK;
+}
+
+}  // namespace
+
+extern "C" int fpm_residual(fpm_ctx *c, double *err, double *ref, double *elapsed_ms) {
+    int rc = admit(c, "fpm_residual", err, ref);
+    if (rc || (rc = ensure_scratch(c))) return rc;
+    const int n = c->prob.n_order;
+    HIP_TRY(hipEventRecord(c->res_ev[0], c->stream));
+    if ((rc = launch_entries(c, c->ident_dev, n))) return rc;
+    HIP_TRY(hipEventRecord(c->res_ev[1], c->stream));
+    if ((rc = copy_sums(c, n, err, ref))) return rc;
+    return finish(c, elapsed_ms);
+}
+
+extern "C" int fpm_residual_at(fpm_ctx *c, const fpm_probe *probes, int n, double *err, double *ref,
+                               double *elapsed_ms) {
+    int rc = admit(c, "fpm_residual_at", err, ref);
+    if (rc) return rc;
+    if (!probes || n < 1) return set_err(FPM_ERR_INVAL, "fpm_residual_at: %s", probes ? "n < 1" : "null probes");
+    // every entry resolved and validated before the first launch
+    const int np = c->st.np, L = c->st.L, n_order = c->prob.n_order;
+    std::vector<ResEntry> ent((size_t)n);
+    for (int k = 0; k < n; ++k) {
+        const fpm_probe &q = probes[k];
+        if (q.pos < 0 || q.pos >= n_order)
+            return set_err(FPM_ERR_INVAL, "fpm_residual_at: entry %d: pos=%d outside order[0, %d)", k, q.pos, n_order);
+        const int led = c->order[q.pos];
+        const long long x = (long long)c->x0[led] + q.dx, y = (long long)c->y0[led] + q.dy;
+        if (x < 0 || x > L - np || y < 0 || y > L - np)
+            return set_err(FPM_ERR_INVAL, "fpm_residual_at: entry %d: window (%lld,%lld) of LED %d leaves the %dx%d "
+                           "spectrum", k, x, y, led, L, L);
+        ent[k] = ResEntry{led, (int)x + np / 2, (int)y + np / 2, 0};
+    }
+    if ((rc = ensure_scratch(c))) return rc;
+    const size_t B = c->st.B;
+    HIP_TRY(hipEventRecord(c->res_ev[0], c->stream));
+    // pieces of n_order entries, what the entry table and the folded sums
+    // hold; everything is ordered on the run stream (ent is pageable: the copy
+    // has left it when hipMemcpyAsync returns), so a piece's table and sums
+    // are free again when the next one overwrites them
+    for (int k0 = 0; k0 < n; k0 += n_order) {
+        const int m = std::min(n_order, n - k0);
+        HIP_TRY(hipMemcpyAsync(c->res_ent, ent.data() + k0, (size_t)m * sizeof(ResEntry), hipMemcpyHostToDevice,
+                               c->stream));
+        if ((rc = launch_entries(c, c->res_ent, m)) ||
+            (rc = copy_sums(c, m, err ? err + k0 * B : nullptr, ref ? ref + k0 * B : nullptr)))
+            return rc;
+    }
+    HIP_TRY(hipEventRecord(c->res_ev[1], c->stream));
+    return finish(c, elapsed_ms);
 }

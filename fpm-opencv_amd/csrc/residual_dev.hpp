@@ -1,7 +1,7 @@
 // residual_dev.hpp -- what the LED step's kernels need to run as the residual
 // sweep's (fpm_residual, residual.hip).  general.hip's K1 / K2 and np256.hip's
 // C are templates over their argument struct: StepArgs is the update step of
-// one LED, ResArgs a batch of LEDs of order[] whose tail sums
+// one LED, ResArgs a batch of (LED, window) entries whose tail sums
 // (|psi| - sqrt(I))^2 and I into one partial per block instead of replacing
 // the amplitude.  The overloads below give both the same front half; the
 // sums are the ResArgs instances' tail.
@@ -31,14 +31,15 @@ __device__ __forceinline__ float res_add(float acc, float2 v, float inv_n2, unsi
     return acc + (2.0f * a < s ? __builtin_fmaf(a, a - 2.0f * s, fi) : d * d);
 }
 
-// The LED a block works on: the step's own, or LED position i0 + z of the
-// batch (centre of its sub-aperture and its stack index)
+// The LED a block works on: the step's own, or entry i0 + z of the batch's
+// list (stack index and centre of its window, launch.hpp ResEntry) in one load
 __device__ __forceinline__ StepArgs res_led(const StepArgs &sa, int, int) { return sa; }
-__device__ __forceinline__ StepArgs res_led(const ResArgs &ra, int z, int np) {
+__device__ __forceinline__ StepArgs res_led(const ResArgs &ra, int z, int) {
+    const int4 e = *reinterpret_cast<const int4 *>(ra.ent + ra.i0 + z);
     StepArgs sa;
-    sa.led = ra.order[ra.i0 + z];
-    sa.xc = ra.x0[sa.led] + np / 2;
-    sa.yc = ra.y0[sa.led] + np / 2;
+    sa.led = e.x;
+    sa.xc = e.y;
+    sa.yc = e.z;
     return sa;
 }
 

@@ -37,12 +37,27 @@
 //                      processing order) and sweep_ms; with --grid the patches
 //                      are the grid's; a figure whose S is 0 (all dark) is null.
 //                      The .npy outputs do not change
+//   --calibrate-leds R LED position calibration: after every iteration but the
+//                      last, a window search of radius R (1 .. 8).  The residual
+//                      of the current state is evaluated with every LED's
+//                      window at each integer offset of the (2R+1)^2
+//                      neighbourhood (fpm_residual_at, one batched sweep), summed
+//                      over the patches; an LED moves to the candidate whose sum
+//                      is strictly smaller than at its tabled position (ties: the
+//                      nearest), and the corrected table replaces the live
+//                      context's (fpm_set_crops).  result.json gains
+//                      "led_calibration": radius, shift_total [used][2] (dx, dy
+//                      in processing order), moved_per_iteration, crop_x0 /
+//                      crop_y0 as used last, probe_ms.  Works with --grid and
+//                      --residual (the sweep then follows the iteration and
+//                      precedes the search)
 //
 // Device selection: OPENCV_OPENCL_DEVICE (set by use_gpu.sh / use_cpu.sh) is
 // read with OpenCV's "<platform>:<type>:<device>" grammar and the scripts'
 // literal "GPU:0" / "CPU:0" form: a CPU type anywhere is refused (exit 3; the
 // CPU restatement is the oracle, not a product path), a GPU index selects the
 // MI355X ordinal; --device overrides it.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -50,6 +65,7 @@
 #include <fstream>
 #include <iostream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/fpm_hip.h"
@@ -151,6 +167,7 @@ int main(int argc, char **argv) {
     std::string out_dir = ".", led_table, path_opt = "auto";
     int device = 0, device_opt = -1, gx = 0, gy = 0;
     bool want_residual = false;
+    int cal_radius = -1;  // --calibrate-leds R: a window search of radius R between the iterations
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--out" && i + 1 < argc) out_dir = argv[++i];
@@ -158,6 +175,13 @@ int main(int argc, char **argv) {
         else if (a == "--led-table" && i + 1 < argc) led_table = argv[++i];
         else if (a == "--path" && i + 1 < argc) path_opt = argv[++i];
         else if (a == "--residual") want_residual = true;
+        else if (a == "--calibrate-leds" && i + 1 < argc) {
+            cal_radius = atoi(argv[++i]);
+            if (cal_radius < 1 || cal_radius > 8) {
+                std::cerr << "--calibrate-leds wants a radius from 1 to 8" << std::endl;
+                return 2;
+            }
+        }
         else if (a == "--grid" && i + 1 < argc) {
             if (sscanf(argv[++i], "%dx%d", &gx, &gy) != 2 || gx < 1 || gy < 1) {
                 std::cerr << "--grid wants GXxGY, e.g. 16x16" << std::endl;
@@ -329,10 +353,52 @@ int main(int argc, char **argv) {
         std::cerr << "fpm: " << fpm_last_error() << std::endl;
         return 1;
     }
+    // --calibrate-leds R: one search step after every iteration but the last.
+    // Every LED's E, summed over the patches, with its window at each offset
+    // of the (2R+1)^2 neighbourhood ((0, 0) first, then by growing distance);
+    // an LED moves to the first candidate whose sum is strictly smaller than at
+    // (0, 0); the corrected table goes to the live context (fpm_set_crops).
+    std::vector<int32_t> cal_x = x0, cal_y = y0, cal_moved;
+    double cal_ms = 0;
+    std::vector<std::pair<int, int>> cal_offs;
+    for (int dy = -cal_radius; dy <= cal_radius; ++dy)
+        for (int dx = -cal_radius; dx <= cal_radius; ++dx) cal_offs.push_back({dx, dy});
+    std::stable_sort(cal_offs.begin(), cal_offs.end(), [](const std::pair<int, int> &a, const std::pair<int, int> &b) {
+        return a.first * a.first + a.second * a.second < b.first * b.first + b.second * b.second;
+    });
+    auto calibrate = [&]() {
+        std::vector<fpm_probe> probes;  // LED-major: an LED's candidates are adjacent
+        for (int i = 0; i < used; ++i)
+            for (auto &o : cal_offs) {
+                const int x = cal_x[i] + o.first, y = cal_y[i] + o.second;
+                if (x >= 0 && x <= L - np && y >= 0 && y <= L - np) probes.push_back({i, o.first, o.second});
+            }
+        std::vector<double> e(probes.size() * (size_t)B);
+        double ms = 0;
+        if (fpm_residual_at(ctx, probes.data(), (int)probes.size(), e.data(), nullptr, &ms)) return false;
+        cal_ms += ms;
+        int moved = 0;
+        for (size_t k = 0, end; k < probes.size(); k = end) {
+            const int i = probes[k].pos;  // its entries are [k, end), (0, 0) first
+            double best = 0;
+            size_t at = k;
+            for (end = k; end < probes.size() && probes[end].pos == i; ++end) {
+                double sum = 0;
+                for (int b = 0; b < B; ++b) sum += e[end * B + b];
+                if (end == k || sum < best) best = sum, at = end;
+            }
+            cal_x[i] += probes[at].dx;
+            cal_y[i] += probes[at].dy;
+            moved += probes[at].dx != 0 || probes[at].dy != 0;
+        }
+        cal_moved.push_back(moved);
+        return moved == 0 || fpm_set_crops(ctx, cal_x.data(), cal_y.data()) == 0;
+    };
     auto t_all = std::chrono::steady_clock::now();
     for (int itr = 1; itr <= itr_count; ++itr) {
         auto t0 = std::chrono::steady_clock::now();
-        if ((rc = fpm_run(ctx, 1)) || (want_residual && !residual())) {
+        if ((rc = fpm_run(ctx, 1)) || (want_residual && !residual()) ||
+            (cal_radius > 0 && itr < itr_count && !calibrate())) {
             std::cerr << "fpm: " << fpm_last_error() << std::endl;
             return 1;
         }
@@ -405,6 +471,18 @@ int main(int argc, char **argv) {
                     put_ratio(f, i ? ", " : "", e, s2);
                 }
                 fprintf(f, "], \"sweep_ms\": %.6f},\n", res_ms);
+            }
+            if (cal_radius > 0) {  // in processing order (stack index i == position i)
+                fprintf(f, "  \"led_calibration\": {\"radius\": %d, \"shift_total\": [", cal_radius);
+                for (int i = 0; i < used; ++i)
+                    fprintf(f, "%s[%d, %d]", i ? ", " : "", cal_x[i] - x0[i], cal_y[i] - y0[i]);
+                fprintf(f, "], \"moved_per_iteration\": [");
+                for (size_t i = 0; i < cal_moved.size(); ++i) fprintf(f, "%s%d", i ? ", " : "", cal_moved[i]);
+                fprintf(f, "], \"crop_x0\": [");
+                for (int i = 0; i < used; ++i) fprintf(f, "%s%d", i ? ", " : "", cal_x[i]);
+                fprintf(f, "], \"crop_y0\": [");
+                for (int i = 0; i < used; ++i) fprintf(f, "%s%d", i ? ", " : "", cal_y[i]);
+                fprintf(f, "], \"probe_ms\": %.6f},\n", cal_ms);
             }
             if (grid) {
                 fprintf(f, "  \"grid\": {\"gx\": %d, \"gy\": %d, \"patches\": %d, \"frame\": [%d, %d], "

@@ -49,7 +49,7 @@ HIP_SYMBOLS = (
     "fpm_download_objcrop_device", "fpm_set_stream", "fpm_get_info",
     "fpm_get_timing", "fpm_runFPM", "fpm_last_error", "fpm_version",
     "fpm_upload_frames", "fpm_download_stack", "fpm_get_info_sized", "fpm_abi_version",
-    "fpm_get_clock", "fpm_residual",
+    "fpm_get_clock", "fpm_residual", "fpm_residual_at", "fpm_set_crops", "fpm_get_crops",
 )
 # test-only entry points (include/fpm_hip_debug.h)
 HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan",
@@ -106,6 +106,10 @@ class fpm_clock(C.Structure):
                 ("ms_per_launch", C.c_double), ("launches", C.c_int32)]
 
 
+class fpm_probe(C.Structure):
+    _fields_ = [("pos", C.c_int32), ("dx", C.c_int32), ("dy", C.c_int32)]
+
+
 class fpm_ladder_kernel(C.Structure):
     _fields_ = [("generation", C.c_int), ("tile", C.c_int), ("threads", C.c_int), ("e", C.c_int),
                 ("grid_x", C.c_int), ("grid_y", C.c_int), ("lds_dynamic", C.c_int), ("lds_static", C.c_int)]
@@ -158,6 +162,10 @@ def load_library(path: str = HIP_LIB):
         "fpm_get_timing": (C.c_int, [vp, C.POINTER(fpm_timing)]),
         "fpm_get_clock": (C.c_int, [vp, C.POINTER(fpm_clock)]),
         "fpm_residual": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "fpm_residual_at": (C.c_int, [vp, C.POINTER(fpm_probe), C.c_int, C.POINTER(C.c_double),
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "fpm_set_crops": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "fpm_get_crops": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "fpm_runFPM": (C.c_int, [C.POINTER(fpm_problem), C.c_int, u16p, C.c_int,
                                  f32p, f32p, f32p, f32p]),
         "fpm_upload_frames": (C.c_int, [vp, C.POINTER(fpm_frames), vp, C.c_int, C.POINTER(C.c_int16)]),
@@ -325,6 +333,44 @@ class Solver:
         dp = C.POINTER(C.c_double)
         _check(_lib.fpm_residual(self._h, err.ctypes.data_as(dp), ref.ctypes.data_as(dp), C.byref(ms)))
         return dict(err=err, ref=ref, ms=ms.value)
+
+    def residual_at(self, pos, dx, dy):
+        """fpm_residual_at: the residual of the current state for the image of
+        order[pos[k]] with its window moved by (dx[k], dy[k]) from the crop
+        table's; equal-length integer arrays.  err / ref are float64
+        [n][n_patch], row k = entry k; read-only, blocking."""
+        pos, dx, dy = _i32(pos).ravel(), _i32(dx).ravel(), _i32(dy).ravel()
+        if not (len(pos) == len(dx) == len(dy)):
+            raise ValueError("pos, dx and dy must have one length")
+        n = len(pos)
+        probes = (fpm_probe * max(n, 1))()
+        for k in range(n):
+            probes[k] = fpm_probe(int(pos[k]), int(dx[k]), int(dy[k]))
+        err = np.empty((n, self.prob.n_patch), np.float64)
+        ref = np.empty_like(err)
+        ms = C.c_double()
+        dp = C.POINTER(C.c_double)
+        _check(_lib.fpm_residual_at(self._h, probes, n, err.ctypes.data_as(dp), ref.ctypes.data_as(dp), C.byref(ms)))
+        return dict(err=err, ref=ref, ms=ms.value)
+
+    def set_crops(self, x0, y0):
+        """fpm_set_crops: replace the crop table [n_stack] of the live context;
+        the state is kept.  Raises FpmError (and changes nothing) when the
+        table is invalid or plans another context than this one."""
+        x0, y0 = _i32(x0).ravel(), _i32(y0).ravel()
+        n = len(self.prob.x0)
+        if len(x0) != n or len(y0) != n:
+            raise ValueError(f"crop tables of {len(x0)} / {len(y0)} entries: want {n}")
+        ip = C.POINTER(C.c_int32)
+        _check(_lib.fpm_set_crops(self._h, x0.ctypes.data_as(ip), y0.ctypes.data_as(ip)))
+
+    def crops(self):
+        """(x0, y0) int32 [n_stack]: the crop table in use (fpm_get_crops)."""
+        n = len(self.prob.x0)
+        x0, y0 = np.empty(n, np.int32), np.empty(n, np.int32)
+        ip = C.POINTER(C.c_int32)
+        _check(_lib.fpm_get_crops(self._h, x0.ctypes.data_as(ip), y0.ctypes.data_as(ip)))
+        return x0, y0
 
     def download(self, objF=True, objCrop=True, pupil=True, support=True):
         p = self.prob

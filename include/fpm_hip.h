@@ -35,8 +35,11 @@ extern "C" {
  * the whole struct, so a caller reading threads_per_wg from it must move to
  * fpm_get_info_sized; fpm_get_clock added; fpm_run refuses a capturing
  * stream.  (6): fpm_residual added.  fpm_abi_version() reports the library's
- * revision. */
+ * revision.  Entry points appended since then change nothing a revision-6
+ * caller sees, so the revision stands and each addition has a feature macro:
+ * FPM_HAS_LED_CALIBRATION = fpm_residual_at, fpm_set_crops, fpm_get_crops. */
 #define FPM_ABI_VERSION   6
+#define FPM_HAS_LED_CALIBRATION 1
 
 #define FPM_OK            0
 #define FPM_ERR_INVAL   (-22)   /* bad argument / unsupported geometry      */
@@ -211,6 +214,43 @@ int  fpm_run(fpm_ctx *ctx, int iters);
  * counted in fpm_info.device_bytes from then on).  Two calls on the same
  * state return the same bits. */
 int  fpm_residual(fpm_ctx *ctx, double *err, double *ref, double *elapsed_ms);
+
+/* The residual of the current state with windows moved: LED position
+ * calibration's search.  Entry k gives E (and S) for the image of order[pos]
+ * with its sub-aperture window at (crop_x0 + dx, crop_y0 + dy) instead of
+ * (crop_x0, crop_y0).
+ *   err, ref [n][n_patch]   as fpm_residual's, row k = probes[k]; either may
+ *                           be NULL, not both
+ * The contract of fpm_residual: read-only, blocking, deterministic;
+ * FPM_ERR_STATE before fpm_init; FPM_ERR_INVAL on a capturing stream.  Every
+ * entry is validated on the host before the first launch: FPM_ERR_INVAL,
+ * naming the entry, when n < 1, when pos is outside [0, n_order), or when a
+ * window leaves the spectrum (0 <= crop + d <= Nlarge - Np must hold in x and
+ * y: fpm_create's rule).  A window may leave the live band of the spectrum:
+ * it reads the stored zeros there.  An entry's value depends on the state and
+ * on that entry alone (not on its neighbours in the list, the batch it ran
+ * in or FPM_RES_BATCH), and (pos, 0, 0) returns the bits of fpm_residual's row
+ * pos.  Entries run in list order, so keep an LED's candidates adjacent: its
+ * image is then read while cached.  n is not limited: lists longer than
+ * n_order run in pieces through the same scratch. */
+typedef struct fpm_probe {
+    int32_t pos;           /* position in order[]                               */
+    int32_t dx, dy;        /* offset of the window from the crop table's        */
+} fpm_probe;
+int  fpm_residual_at(fpm_ctx *ctx, const fpm_probe *probes, int n, double *err, double *ref,
+                     double *elapsed_ms);
+
+/* Replace the crop table ([n_stack] each, validated as by fpm_create) of a
+ * live context; spectrum, pupil, stack and everything the caller holds stay
+ * valid.  Legal before and after fpm_init and between fpm_run calls; blocking
+ * (waits for the run stream); FPM_ERR_INVAL on a capturing stream.  The new
+ * table must plan the context fpm_create planned (same kernels, launch shapes
+ * and LDS fits, judged with the live band grown to hold the old and the new
+ * windows); otherwise FPM_ERR_INVAL with the reason, and the context is
+ * unchanged: create a new one for such a table.  fpm_get_crops copies the
+ * table in use. */
+int  fpm_set_crops(fpm_ctx *ctx, const int32_t *crop_x0, const int32_t *crop_y0);
+int  fpm_get_crops(const fpm_ctx *ctx, int32_t *crop_x0, int32_t *crop_y0);
 
 /* Wait for all work on the context stream. */
 int  fpm_synchronize(fpm_ctx *ctx);
