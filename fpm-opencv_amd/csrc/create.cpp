@@ -327,6 +327,7 @@ int allocate(fpm_ctx *c) {
     get(&st.pmax, B * st.npart);
     get(&c->disk_dev, c->disk.size());
     get(&c->meas, stack_elems(c));
+    get(&c->gain_dev, stack_images(c));
     get(&c->order_dev, c->order.size());
     get(&c->x0_dev, c->x0.size());
     get(&c->y0_dev, c->y0.size());
@@ -356,6 +357,7 @@ int allocate(fpm_ctx *c) {
     get(&c->tw_L, (size_t)st.L);
     if (rc) return rc;
     st.meas = c->meas;
+    st.gain = c->gain_dev;
     st.disk = c->disk_dev;
     st.clk = c->clk;
     for (int g = 1; g < c->ngroups; ++g) {
@@ -385,8 +387,9 @@ bool upload_crops(fpm_ctx *c) {
 
 int upload_tables(fpm_ctx *c) {
     const auto twn = twiddles(c->st.np), twl = twiddles(c->st.L);
+    c->gain.assign(stack_images(c), 1.0f);
     if (!put(c->tw_np, twn) || !put(c->tw_L, twl) || !put(c->disk_dev, c->disk) || !put(c->order_dev, c->order) ||
-        !upload_crops(c))
+        !put(c->gain_dev, c->gain) || !upload_crops(c))
         return set_err(FPM_ERR_DEVICE, "table upload failed");
     return FPM_OK;
 }
@@ -408,12 +411,13 @@ const char *plan_difference(const fpm_ctx *a, const fpm_ctx *b) {
     if (a->st.npart != b->st.npart) return "the pupil-maximum partials";
     const ResidualPlan &p = a->rplan, &q = b->rplan;
     if (p.kind != q.kind || p.nblk != q.nblk || p.nl != q.nl || p.t_led != q.t_led || !same_kernel(p.rows, q.rows) ||
-        !same_kernel(p.cols, q.cols))
+        !same_kernel(p.cols, q.cols) || !same_kernel(p.cols_gain, q.cols_gain) || !same_kernel(p.cols_mom, q.cols_mom))
         return "the residual sweep's plan";
     for (int g = 0; !a->fused() && g < a->ngroups; ++g) {
         const GeneralPlan &u = a->gplan[g], &v = b->gplan[g];
         if (u.kind != v.kind || (u.kind == GeneralPlan::Lds && (!same_kernel(u.k1, v.k1) || !same_kernel(u.k2, v.k2) ||
-                                                                 !same_kernel(u.k3, v.k3))))
+                                                                 !same_kernel(u.k3, v.k3) ||
+                                                                 !same_kernel(u.k3_gain, v.k3_gain))))
             return "the general path's step plan";
     }
     return nullptr;
@@ -467,7 +471,7 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
         return rc;
     if (!c->fused())
         for (int g = 0; g < c->ngroups && c->general_kind == GeneralPlan::Lds; ++g)
-            HIP_TRY(allow_large_lds({&c->gplan[g].k1, &c->gplan[g].k2, &c->gplan[g].k3}, lds_limit));
+            HIP_TRY(allow_large_lds({&c->gplan[g].k1, &c->gplan[g].k2, &c->gplan[g].k3, &c->gplan[g].k3_gain}, lds_limit));
     *out = c.release();
     return FPM_OK;
 }
@@ -529,6 +533,46 @@ int fpm_set_crops(fpm_ctx *c, const int32_t *crop_x0, const int32_t *crop_y0) {
     return FPM_OK;
 }
 
+int fpm_get_gains(const fpm_ctx *c, float *gain) {
+    if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
+    if (!gain) return set_err(FPM_ERR_INVAL, "fpm_get_gains: null gain");
+    std::copy(c->gain.begin(), c->gain.end(), gain);
+    return FPM_OK;
+}
+
+int fpm_set_gains(fpm_ctx *c, const float *gain) {
+    if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
+    const size_t n = stack_images(c);
+    // fp16 storage holds |objF| hscale <= max sqrt(I) <= 256 (fpm_state.hpp): a
+    // gain multiplies the amplitude, so 256 g must stay below the largest half
+    const bool fp16 = (c->prob.flags & FPM_FLAG_SPEC_FP16) != 0;
+    for (size_t i = 0; gain && i < n; ++i) {
+        const float g = gain[i];
+        if (!std::isfinite(g) || !(g > 0.f))
+            return set_err(FPM_ERR_INVAL, "fpm_set_gains: gain[%zu] (LED %zu, patch %zu) = %g is not finite and > 0", i,
+                           i / c->st.B, i % c->st.B, (double)g);
+        if (fp16 && !(256.0f * g < 65504.0f))
+            return set_err(FPM_ERR_INVAL, "fpm_set_gains: gain[%zu] (LED %zu, patch %zu) = %g: under FPM_FLAG_SPEC_FP16 "
+                           "256 g must stay below 65504", i, i / c->st.B, i % c->st.B, (double)g);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = refuse_capture(c, "fpm_set_gains");
+    if (rc) return rc;
+    // nothing in flight reads the table while it changes.  Its address stays, and
+    // every kernel (a captured graph's included) loads its gain from it at run
+    // time, so the general path's graphs stay valid while the table keeps its kind
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    std::vector<float> g(n, 1.0f);
+    if (gain) g.assign(gain, gain + n);
+    if (!put(c->gain_dev, g)) return set_err(FPM_ERR_DEVICE, "fpm_set_gains: table upload failed");
+    c->gain.swap(g);
+    const bool unit = std::all_of(c->gain.begin(), c->gain.end(), [](float v) { return v == 1.0f; });
+    // the general path's graphs hold the update kernels of the other kind: the next fpm_run captures again
+    if (unit != c->gains_unit) c->drop_graphs();
+    c->gains_unit = unit;
+    return FPM_OK;
+}
+
 int fpm_set_stream(fpm_ctx *c, void *s) {
     if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
     c->stream = s ? (hipStream_t)s : c->own_stream;
@@ -560,7 +604,7 @@ int fpm_debug_plan_ladder(int np, int nb, int B, int step, int no_wave_cols, int
     st.np = np;
     st.nb = nb;
     st.B = B;
-    StepKernel rows, cols;
+    StepKernel rows, cols, cols_gain, cols_mom;
     LdsLadder l;
     size_t row_static;
     if (step) {
@@ -569,7 +613,7 @@ int fpm_debug_plan_ladder(int np, int nb, int B, int step, int no_wave_cols, int
         row_static = std::max(p.k1.lds_static, p.k3.lds_static);
     } else {
         l = plan_lds_ladder(pl, np, nb, B, sw, false);
-        residual_lds_kernels(l, rows, cols);
+        residual_lds_kernels(l, rows, cols, cols_gain, cols_mom);
         row_static = rows.lds_static;
     }
     out->rows = ladder_kernel(rows, l.row_e, 0, row_static);
@@ -596,7 +640,9 @@ int fpm_debug_get_ladder(const fpm_ctx *c, int residual, fpm_ladder *out) {
         if (p.kind != ResidualPlan::Lds) return set_err(FPM_ERR_INVAL, "the residual sweep runs the register pair");
         HIP_TRY(hipSetDevice(c->device));
         int rc = static_lds_matches(p.rows);
-        if (rc || (rc = static_lds_matches(p.cols))) return rc;
+        if (rc || (rc = static_lds_matches(p.cols)) || (rc = static_lds_matches(p.cols_gain)) ||
+            (rc = static_lds_matches(p.cols_mom)))
+            return rc;
         out->rows = ladder_kernel(p.rows, p.ladder.row_e, 0, p.rows.lds_static);
         out->cols = ladder_kernel(p.cols, p.ladder.col_e, p.ladder.cw, p.cols.lds_static);
         return FPM_OK;
@@ -604,7 +650,9 @@ int fpm_debug_get_ladder(const fpm_ctx *c, int residual, fpm_ladder *out) {
     const GeneralPlan &p = c->gplan[0];
     HIP_TRY(hipSetDevice(c->device));
     int rc = static_lds_matches(p.k1);
-    if (rc || (rc = static_lds_matches(p.k2)) || (rc = static_lds_matches(p.k3))) return rc;
+    if (rc || (rc = static_lds_matches(p.k2)) || (rc = static_lds_matches(p.k3)) ||
+        (rc = static_lds_matches(p.k3_gain)))
+        return rc;
     out->rows = ladder_kernel(p.k1, p.ladder.row_e, 0, std::max(p.k1.lds_static, p.k3.lds_static));
     out->cols = ladder_kernel(p.k2, p.ladder.col_e, p.ladder.cw, p.k2.lds_static);
     return FPM_OK;

@@ -1,9 +1,10 @@
 // ctx.hpp -- the context behind the extern "C" boundary of libfpm_hip.so
 // (include/fpm_hip.h), shared by the files that implement it:
-//   create.cpp    validate, plan, allocate, destroy; fpm_set_crops / fpm_get_crops
+//   create.cpp    validate, plan, allocate, destroy; fpm_set_crops / fpm_get_crops,
+//                 fpm_set_gains / fpm_get_gains
 //   transfer.cpp  the stack uploads and the downloads
 //   run.cpp       fpm_init, fpm_run, the general path's patch groups and graphs
-//   residual_api.cpp  fpm_residual, fpm_residual_at (kernels: residual.hip)
+//   residual_api.cpp  fpm_residual, fpm_residual_at, fpm_moments (kernels: residual.hip)
 //   api.cpp       errors, version, info, timing, clock, fpm_runFPM
 // Errors are negative codes plus fpm_last_error(); nothing here ever falls
 // back to a CPU path.
@@ -100,6 +101,12 @@ struct fpm_ctx {
     float2 *tw_np = nullptr, *tw_L = nullptr;
     float2 *objcrop = nullptr;
     uint16_t *meas = nullptr;
+    // LED gains [n_stack][B] (fpm_set_gains): the host copy fpm_get_gains returns
+    // and the device table the kernels read at every launch (DevState::gain), so
+    // a captured graph of the general path never holds a gain by value
+    std::vector<float> gain;
+    float *gain_dev = nullptr;
+    bool gains_unit = true;         // every gain is 1.0f: fpm_residual launches its ungained kernels
     float2 *xch = nullptr;          // split / distributed mode: exchange area
     int *split_flags = nullptr;     //   handoff flags [KS B] + sticky abort flag + XCC ids [KS B]
     int stall_led = -1;             //   fpm_debug_set_stall (tests): the last part stops publishing
@@ -135,6 +142,9 @@ struct fpm_ctx {
     unsigned long long *res_pref = nullptr;
     hipEvent_t res_ev[2] = {};
     bool res_ready = false;         // all of the above exist
+    // fpm_moments' own: the per-block partials and the folded sums of C
+    double *res_pcross = nullptr, *res_cross = nullptr;
+    bool mom_ready = false;
 
     fpm_ctx() = default;
     fpm_ctx(const fpm_ctx &) = delete;

@@ -17,7 +17,7 @@ __global__ void k_slot_update(const float2 *f, const float2 *o, const float2 *p,
     if (i >= n) return;
     float2 nm;
     float a;
-    nv[i] = slot_update(f[i], o[i], p[i], pm[i], st, nm, a);
+    nv[i] = slot_update<false>(f[i], o[i], p[i], pm[i], 1.0f, st, nm, a);
     num[i] = nm;
     oa[i] = a;
 }

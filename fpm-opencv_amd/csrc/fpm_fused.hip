@@ -73,7 +73,7 @@ struct FzCfg {
 
 // KS workgroups per patch: 1 (both column halves in turn), or split mode with
 // 2 / 4 workgroups each owning one column part
-template <int NT, int KS>
+template <int NT, int KS, bool GAIN>
 __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
     using namespace fz;
     using C = FzCfg<NT>;
@@ -309,6 +309,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
         const int led = lp.led, xc = lp.xc, yc = lp.yc;
         float2 *srow = spec + (unsigned)(yc * L + xc);   // spec[yc + ky][xc + kx] = srow[ky*L + kx]
         const uint16_t *Ib = a.meas + ((size_t)led * st.B + b) * NP * NP;
+        const float gl = fused_gain<GAIN>(st, led, b);  // used by the update, a whole LED step later
 
         // ---- gather the sub-aperture on the support (pre-update Objfcrop,
         // fpmMain.cpp:358-362); the tail pixels' O was loaded with Opre
@@ -604,7 +605,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
                 float2 num = make_float2(0.f, 0.f);
                 if ((inmask[j] >> s) & 1) {
                     float oa;
-                    const float2 nv = slot_update(F[j][s], Opre[j][s], P[j][s], pm, st, num, oa);
+                    const float2 nv = slot_update<GAIN>(F[j][s], Opre[j][s], P[j][s], pm, gl, st, num, oa);
                     sst(srow + (kyr[j] * L + t) + soff(s), nv);  // read by a split partner
                     note(yc + kyr[j], xc + slot_kx(t, s), oa, cmag(nv));
                 }
@@ -617,7 +618,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
             // D = Objfup - ObjfcropP with ObjfcropP = tailX (gathered O*P): pass F = tailF
             // and the slot helper recomputes O*P the same way the gather did
             float oa;
-            const float2 nv = slot_update(tailF[tid], Ot, Pt, pm, st, NPt, oa);
+            const float2 nv = slot_update<GAIN>(tailF[tid], Ot, Pt, pm, gl, st, NPt, oa);
             sst(srow + tp.x * L + tp.y, nv);
             note(yc + tp.x, xc + tp.y, oa, cmag(nv));
         }
@@ -797,8 +798,14 @@ hipError_t launch_fused_iteration(const DevState &st, const FusedLaunch &in, int
     if (lds0 > kLdsCap) return hipErrorInvalidValue;
     size_t lds;  // + the LED table when it fits
     a.ledtab_off = ledtab_offset(lds0, in.n_order, st.L, kLdsCap, lds, in.no_ledtab);
-    if (ks == 1) return launch_lds(k_fused_iteration<512, 1>, st.B, 512, lds, &a, s);
-    return launch_np256_parts(ks == 4 ? k_fused_iteration<512, 4> : k_fused_iteration<512, 2>, ks, lds, &a, s);
+    if (in.gains) {
+        if (ks == 1) return launch_lds(k_fused_iteration<512, 1, true>, st.B, 512, lds, &a, s);
+        return launch_np256_parts(ks == 4 ? k_fused_iteration<512, 4, true> : k_fused_iteration<512, 2, true>, ks, lds, &a,
+                                  s);
+    }
+    if (ks == 1) return launch_lds(k_fused_iteration<512, 1, false>, st.B, 512, lds, &a, s);
+    return launch_np256_parts(ks == 4 ? k_fused_iteration<512, 4, false> : k_fused_iteration<512, 2, false>, ks, lds, &a,
+                              s);
 }
 
 }  // namespace fpm

@@ -13,6 +13,7 @@
 //                               (fpmMain.cpp:312,472), so the Np x Np pupil is
 //                               never stored densely.
 //   meas   u16    [nS][B][Np][Np]  LED-major measurement stack.
+//   gain   float  [nS][B]       per-image amplitude factor (fpm_set_gains), 1 by default.
 //   tmax   float  [B][nty][ntx] max |spec| per 16x16 tile: the exact global
 //                               max|objF| of fpmMain.cpp:460,467 without an
 //                               L x L pass per LED.
@@ -83,6 +84,10 @@ struct DevState {
     // launch clock probe of the fused kernels (fused_sync.hpp ClockProbe):
     // [3] = block 0's shader cycles, 100 MHz ticks, launches; null = off
     unsigned long long *clk;
+    // [nS][mB] LED gains (fpm_set_gains), LED-major like meas, all ones by
+    // default: wherever a kernel uses a measured amplitude it is g sqrt(I).
+    // (Last, so every older field keeps its kernel-argument offset.)
+    const float *gain;
 };
 
 // patches [b0, b0 + n) of a context as a DevState of n patches (the general
@@ -95,6 +100,7 @@ inline DevState patch_view(const DevState &st, int b0, int n) {
     if (v.spec16) v.spec16 += b0 * L2;
     if (v.pupil) v.pupil += b0 * nb2;
     if (v.meas) v.meas += (size_t)b0 * st.np * st.np;
+    if (v.gain) v.gain += b0;
     if (v.T) v.T += (size_t)b0 * st.nb * st.np;
     if (v.T16) v.T16 += (size_t)b0 * st.nb * st.np;
     if (v.tsr) v.tsr += (size_t)b0 * st.nb;
@@ -123,6 +129,23 @@ __device__ __forceinline__ void spec_st(const DevState &st, int b, size_t i, flo
         st.spec16[o] = __float22half2_rn(make_float2(v.x * st.hscale, v.y * st.hscale));
     else
         st.spec[o] = v;
+}
+
+// Gain of LED `led` for patch b (DevState::gain): the one scalar an LED step
+// needs.  Both indices are workgroup-uniform, so the load goes through the
+// scalar cache into an SGPR; every kernel issues it where it learns the LED,
+// a transform or more ahead of the update that uses it.
+__device__ __forceinline__ float led_gain(const DevState &st, int led, int b) {
+    return st.gain[(size_t)__builtin_amdgcn_readfirstlane(led) * st.mB + __builtin_amdgcn_readfirstlane(b)];
+}
+
+// The gain an LED-update kernel's GAIN instance uses (slot_update,
+// general_update): loaded where the kernel learns the LED, ahead of its use;
+// no load without GAIN
+template <bool GAIN>
+__device__ __forceinline__ float fused_gain(const DevState &st, int led, int b) {
+    if constexpr (GAIN) return led_gain(st, led, b);
+    else return 1.0f;
 }
 
 // block scale of fp16 scratch: a power of two s with m s < 2^14 for the

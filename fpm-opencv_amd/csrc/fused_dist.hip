@@ -60,7 +60,7 @@ constexpr int kWinTiles = 64;                         // window tiles published 
 constexpr size_t dist_patch_elems(int ks) { return (size_t)kTgRows * fz::NP + (size_t)ks * kWinTiles + ks; }
 }  // namespace
 
-template <int KS>
+template <int KS, bool GAIN>
 __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
     using namespace fz;
     constexpr int NT = 512, NG = 32, NW = 8;
@@ -278,6 +278,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
         const int led = lp.led, xc = lp.xc, yc = lp.yc;
         const int wb0 = yc * L + xc;
         const uint16_t *Ib = a.meas + ((size_t)led * st.B + b) * NP * NP;
+        const float gl = fused_gain<GAIN>(st, led, b);  // used by the update, a whole LED step later
         Tw wt;
         wt.load(tw2, t);
         float2 v[16], r[16];
@@ -524,7 +525,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
                 float2 num = make_float2(0.f, 0.f);
                 if (rowi < a.n_fft_rows && ky * ky + kx * kx <= R * R) {
                     float oa;
-                    const float2 nv = slot_update(upd_f[i], upd_o[i], upd_p[i], pm, st, num, oa);
+                    const float2 nv = slot_update<GAIN>(upd_f[i], upd_o[i], upd_p[i], pm, gl, st, num, oa);
                     cst(rs, wb0 + ky * L + kx, nv);
                     note(yc + ky, xc + kx, oa, cmag(nv));
                 }
@@ -536,7 +537,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
                 float2 num = make_float2(0.f, 0.f);
                 if ((inmask >> s) & 1) {
                     float oa;
-                    const float2 nv = slot_update(F[s], Opre[s], P[s], pm, st, num, oa);
+                    const float2 nv = slot_update<GAIN>(F[s], Opre[s], P[s], pm, gl, st, num, oa);
                     cst(rs, wb0 + kyr * L + t + soff(s), nv);
                     note(yc + kyr, xc + slot_kx(t, s), oa, cmag(nv));
                 }
@@ -545,7 +546,7 @@ __global__ void __launch_bounds__(512, 1) k_fused_dist(FusedArgs a) {
         }
         if (towner) {
             float oa;
-            const float2 nv = slot_update(tailF[ti], Ot, Pt, pm, st, NPt, oa);
+            const float2 nv = slot_update<GAIN>(tailF[ti], Ot, Pt, pm, gl, st, NPt, oa);
             cst(rs, wb0 + tp.x * L + tp.y, nv);
             note(yc + tp.x, xc + tp.y, oa, cmag(nv));
         }
@@ -776,7 +777,11 @@ hipError_t launch_fused_dist(const DevState &st, const FusedLaunch &in, int ks, 
     if (lds0 > kLdsCap) return hipErrorInvalidValue;
     size_t lds;  // + the LED table when it fits
     a.ledtab_off = ledtab_offset(lds0, in.n_order, st.L, kLdsCap, lds, in.no_ledtab);
-    return launch_np256_parts(ks == 8 ? k_fused_dist<8> : ks == 4 ? k_fused_dist<4> : k_fused_dist<2>, ks, lds, &a, s);
+    if (in.gains)
+        return launch_np256_parts(ks == 8 ? k_fused_dist<8, true> : ks == 4 ? k_fused_dist<4, true> : k_fused_dist<2, true>,
+                                  ks, lds, &a, s);
+    return launch_np256_parts(ks == 8 ? k_fused_dist<8, false> : ks == 4 ? k_fused_dist<4, false> : k_fused_dist<2, false>,
+                              ks, lds, &a, s);
 }
 
 }  // namespace fpm

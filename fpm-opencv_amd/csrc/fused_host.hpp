@@ -37,6 +37,7 @@ struct FusedLaunch {
     unsigned long long *dbg; // FPM_STAMPS=1 phase cycles, else null
     bool dense;              // FPM_S90_DENSE=1 / FPM_MR_DENSE=1: the kernel's dense LDS layout
     bool no_ledtab;          // FPM_NO_LEDTAB=1: no LDS LED table, the global tables instead (ledtab.hpp)
+    bool gains;              // some LED gain is not 1 (fpm_set_gains): the kernels' GAIN instances
 };
 
 // one workgroup-sized dynamic-LDS launch: raise the kernel's limit, launch,

@@ -99,6 +99,7 @@ __device__ __forceinline__ int mr_slot_k(int s) { return fm::SK[s]; }
 // signed frequency of slot s on lane l: l + 10 SK[s] (- Np for the upper slots)
 __device__ __forceinline__ int mr_kx(int l, int s) { return l + 10 * fm::SK[s] - (fm::SK[s] >= 10 ? fm::NP : 0); }
 
+template <bool GAIN>
 __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
     using namespace fm;
     ClockProbe probe;
@@ -202,6 +203,7 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
         const int led = lp.led, xc = lp.xc, yc = lp.yc;
         float2 *srow = spec + (unsigned)(yc * L + xc);
         const uint16_t *Ib = a.meas + ((size_t)led * st.B + b) * NP * NP;
+        const float gl = fused_gain<GAIN>(st, led, b);  // used by the update, a whole LED step later
         float2 v[20];
 
         // ---- A: row IDFTs of the box rows of O*P (:358-365) -> T
@@ -303,7 +305,7 @@ __global__ void __launch_bounds__(fm::NT, 1) k_fused_mr(FusedMRArgs a) {
                 float2 num = make_float2(0.f, 0.f);
                 if ((inmask >> s) & 1) {
                     float oa;
-                    const float2 nv = slot_update(F[s], Opre[s], P[s], pm, st, num, oa);
+                    const float2 nv = slot_update<GAIN>(F[s], Opre[s], P[s], pm, gl, st, num, oa);
                     (srow + (kyr * L + l))[soff(s)] = nv;
                     note(yc + kyr, xc + mr_kx(l, s), oa, cmag(nv));
                 }
@@ -467,7 +469,7 @@ hipError_t launch_fused_mr_iteration(const DevState &st, const FusedLaunch &in, 
     size_t lds;  // the kernel's own LDS + the LED table when it fits
     a.ledtab_off = ledtab_offset(mr_lds_bytes(st.nb, a.band.nbt, a.xw, a.tld), in.n_order, st.L, kLdsCap, lds,
                                  in.no_ledtab);
-    return launch_lds(k_fused_mr, st.B, fm::NT, lds, &a, s);
+    return launch_lds(in.gains ? k_fused_mr<true> : k_fused_mr<false>, st.B, fm::NT, lds, &a, s);
 }
 
 }  // namespace fpm

@@ -84,6 +84,7 @@ struct FusedS90Args {
 // signed frequency of FFT index n (|k| <= r <= 44 lies on the right side of the fold)
 __device__ __forceinline__ int f90_fold(int n) { return n < f90::NP / 2 ? n : n - f90::NP; }
 
+template <bool GAIN>
 __global__ void __launch_bounds__(f90::NT, 1) k_fused_s90(FusedS90Args a) {
     using namespace f90;
     ClockProbe probe;
@@ -187,6 +188,7 @@ __global__ void __launch_bounds__(f90::NT, 1) k_fused_s90(FusedS90Args a) {
         const int led = lp.led, xc = lp.xc, yc = lp.yc;
         float2 *srow = spec + (unsigned)(yc * L + xc);
         const uint16_t *Ib = a.meas + ((size_t)led * st.B + b) * NP * NP;
+        const float gl = fused_gain<GAIN>(st, led, b);  // used by the update, a whole LED step later
         float2 v[10];
 
         // ---- A: row IDFT of box row g of O*P (:358-365) -> T
@@ -272,7 +274,7 @@ __global__ void __launch_bounds__(f90::NT, 1) k_fused_s90(FusedS90Args a) {
             if ((inmask >> k) & 1) {
                 float2 num;
                 float oa;
-                const float2 nv = slot_update(F[k], Opre[k], P[k], pm, st, num, oa);
+                const float2 nv = slot_update<GAIN>(F[k], Opre[k], P[k], pm, gl, st, num, oa);
                 th[g * TLD + k * 10 + l] = num;
                 const int kx = f90_fold(l + 10 * k);
                 srow[kyr * L + kx] = nv;
@@ -437,7 +439,7 @@ hipError_t launch_fused_s90_iteration(const DevState &st, const FusedLaunch &in,
     size_t lds;  // the kernel's own LDS + the LED table when it fits
     a.ledtab_off = ledtab_offset(s90_lds_bytes(st.nb, a.nbt, a.xw, a.tld), in.n_order, st.L, kLdsCap, lds,
                                  in.no_ledtab);
-    return launch_lds(k_fused_s90, st.B, f90::NT, lds, &a, s);
+    return launch_lds(in.gains ? k_fused_s90<true> : k_fused_s90<false>, st.B, f90::NT, lds, &a, s);
 }
 
 }  // namespace fpm

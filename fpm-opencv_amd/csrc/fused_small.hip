@@ -64,7 +64,7 @@ struct SmallArgs {
 // four passes and, with a radix switch at each of the four call sites, more
 // registers: 1.89 M -> 3.19 M LED-updates/s at config 2); NPC = 0: any
 // Np <= 96 with the runtime plan
-template <int NPC>
+template <int NPC, bool GAIN>
 __global__ void __launch_bounds__(fs::NT, 1) k_fused_small(SmallArgs a) {
     using namespace fs;
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
@@ -158,6 +158,7 @@ __global__ void __launch_bounds__(fs::NT, 1) k_fused_small(SmallArgs a) {
         const int xc = a.x0[led] + Np / 2, yc = a.y0[led] + Np / 2;
         float2 *srow = spec + (unsigned)(yc * L + xc);  // spec[yc + ky][xc + kx] = srow[ky*L + kx]
         const uint16_t *Ib = a.meas + ((size_t)led * st.B + b) * NN;
+        const float gl = fused_gain<GAIN>(st, led, b);  // used by the update, a whole LED step later
 
         const float2 *F;
         if constexpr (NPC == 90) {
@@ -274,7 +275,7 @@ __global__ void __launch_bounds__(fs::NT, 1) k_fused_small(SmallArgs a) {
                 pix(i, ky, kx);
                 float oa;
                 const float2 nv =
-                    slot_update(F[(ky + R) * Np + fidx(kx)], Op[i], P[i], pm, st, NUM[i], oa);
+                    slot_update<GAIN>(F[(ky + R) * Np + fidx(kx)], Op[i], P[i], pm, gl, st, NUM[i], oa);
                 srow[ky * L + kx] = nv;
                 note(yc + ky, xc + kx, oa, cmag(nv));
             }
@@ -405,8 +406,9 @@ hipError_t launch_fused_small_iteration(const DevState &st, const FusedLaunch &i
     a.n_order = in.n_order;
     a.band = band_of(st);
     // Np 90 (configs 1/2): the instance with the transform fixed at compile time
-    return launch_lds(st.np == 90 ? k_fused_small<90> : k_fused_small<0>, st.B, fs::NT,
-                      small_lds_bytes(st.np, a.band.nbt), &a, s);
+    const auto fn = in.gains ? (st.np == 90 ? k_fused_small<90, true> : k_fused_small<0, true>)
+                             : (st.np == 90 ? k_fused_small<90, false> : k_fused_small<0, false>);
+    return launch_lds(fn, st.B, fs::NT, small_lds_bytes(st.np, a.band.nbt), &a, s);
 }
 
 }  // namespace fpm

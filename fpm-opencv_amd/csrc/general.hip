@@ -98,6 +98,7 @@ __global__ void __launch_bounds__(256) k_colpass(DevState st, A a, FftPlan pl,
     const int np = st.np, r = st.r, nb = st.nb;
     const int x = blockIdx.x, b = blockIdx.y, z = kIsRes<A> ? blockIdx.z : 0;
     const StepArgs sa = res_led(a, z, np);
+    [[maybe_unused]] const float rg_led = res_gain<A>(st, sa.led, b);
     float2 *bufa = smem, *bufb = smem + np;
     float2 *T = res_T(st, a, z, b, 0, np);
     for (int i = threadIdx.x; i < np; i += blockDim.x) bufa[i] = make_float2(0.f, 0.f);
@@ -113,25 +114,22 @@ __global__ void __launch_bounds__(256) k_colpass(DevState st, A a, FftPlan pl,
     const uint16_t *I = st.meas + ((size_t)sa.led * st.mB + b) * np * np;
     if constexpr (kIsRes<A>) {
         const int g = st.meas_g;
-        float acc = 0.f;
-        unsigned isum = 0;
+        ResAcc<A> acc(rg_led);
         if (g) {  // uniform: the stored column x is contiguous, position p holds row (p mod (Np/g)) g + p / (Np/g)
             const int npg = np / g;
             const float rnpg = 1.0f / (float)npg;
             for (int p = threadIdx.x; p < np; p += blockDim.x) {
                 const int t = udiv(p, npg, rnpg), m = p - t * npg;
                 const unsigned iv = I[(size_t)x * np + p];
-                acc = res_add(acc, res[m * g + t], inv_n2, iv);
-                isum += iv;
+                acc.add(res[m * g + t], inv_n2, iv);
             }
         } else {
             for (int y = threadIdx.x; y < np; y += blockDim.x) {
                 const unsigned iv = I[(size_t)y * np + x];
-                acc = res_add(acc, res[y], inv_n2, iv);
-                isum += iv;
+                acc.add(res[y], inv_n2, iv);
             }
         }
-        res_block_partial<4>(acc, isum, a, ((size_t)z * st.B + b) * a.nblk + x);
+        res_block_partial<4>(acc, a, ((size_t)z * st.B + b) * a.nblk + x);
     } else {
         for (int y = threadIdx.x; y < np; y += blockDim.x) res[y] = amp_replace(res[y], inv_n2, I[(size_t)y * np + x], st);
         __syncthreads();
@@ -143,12 +141,14 @@ __global__ void __launch_bounds__(256) k_colpass(DevState st, A a, FftPlan pl,
 // ---- K3 ---------------------------------------------------------------------
 // grid (nb, B), block 256, LDS 2*Np float2
 constexpr size_t kLdsRowfftUpdate = 4 * sizeof(float);  // red
+template <bool GAIN>
 __global__ void __launch_bounds__(256) k_rowfft_update(DevState st, StepArgs sa, FftPlan pl,
                                                        const float2 *__restrict__ tw) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
     const int np = st.np, r = st.r, nb = st.nb;
     const int row = blockIdx.x, b = blockIdx.y;
     const int ky = row - r;
+    const float gl = fused_gain<GAIN>(st, sa.led, b);
     float2 *bufa = smem, *bufb = smem + np;
     const float2 *T = st.T + ((size_t)b * nb + row) * np;
     for (int i = threadIdx.x; i < np; i += blockDim.x) bufa[i] = T[i];
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(256) k_rowfft_update(DevState st, StepArgs sa,
         const float2 p = pup[row * nb + j];
         const float2 F = res[(kx + np) % np];    // Objfup (:394)
         float2 num;
-        spec_st(st, b, si, general_update(F, o, p, pm, st, num));
+        spec_st(st, b, si, general_update<GAIN>(F, o, p, pm, gl, st, num));
         dP[row * nb + j] = num;
     }
 }
@@ -342,7 +342,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
     }
 }
 
-template <int NT, int E>
+template <int NT, int E, bool GAIN>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16 ? 4 : 1))) k_rowfft_update_tiled(DevState st, StepArgs sa, FftPlan pl,
                                                             const float2 *__restrict__ tw, int lc) {
     extern __shared__ __attribute__((aligned(16))) float2 smem[];
@@ -351,6 +351,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
     const int np = st.np, r = st.r, nb = st.nb, C = 1 << lc, lss = row_pitch(np, lc);
     const int j0 = blockIdx.x << lc, b = blockIdx.y;
     const int cs = min(C, nb - j0);
+    const float gl = fused_gain<GAIN>(st, sa.led, b);
     float2 *tile = smem, *stw = smem + (size_t)C * lss;
     for (int i = threadIdx.x; i < np; i += NT) stw[i] = tw[i];
     const float2 *T = st.T + ((size_t)b * nb + j0) * np;
@@ -376,7 +377,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
         const float2 p = pup[row * nb + j];
         const float2 F = tile[c * lss + (kx < 0 ? kx + np : kx)];  // Objfup (:394)
         float2 num;
-        spec_st(st, b, si, general_update(F, o, p, pm, st, num));
+        spec_st(st, b, si, general_update<GAIN>(F, o, p, pm, gl, st, num));
         dP[row * nb + j] = num;
     }
 }
@@ -398,6 +399,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
     const int np = st.np, r = st.r, nb = st.nb, C = 1 << lc, cm = C - 1;
     const int x0 = blockIdx.x << lc, b = blockIdx.y, z = kIsRes<A> ? blockIdx.z : 0;
     const StepArgs sa = res_led(a, z, np);
+    [[maybe_unused]] const float rg_led = res_gain<A>(st, sa.led, b);
     const int cs = min(C, np - x0);            // columns present in this tile
     float2 *tile = smem;                       // np * C
     float2 *stw = smem + (size_t)np * C;       // np twiddles
@@ -423,8 +425,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
         // order instead would put a wave's 64 LDS reads 2^lc g rows apart, all in
         // one bank.)
         const int g = st.meas_g;
-        float acc = 0.f;
-        unsigned isum = 0;
+        ResAcc<A> acc(rg_led);
         const int npg = g ? np / g : 1;
         const float rg = 1.0f / (float)(g ? g : 1);
         for (int idx = threadIdx.x; idx < np * C; idx += NT) {
@@ -432,10 +433,9 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
             if (c >= cs) continue;
             const int m = udiv(y, g ? g : 1, rg), t = y - m * g;  // g > 0: y = t + g m
             const unsigned iv = g ? I[(size_t)(x0 + c) * np + t * npg + m] : I[(size_t)y * np + x0 + c];
-            acc = res_add(acc, tile[idx], inv_n2, iv);
-            isum += iv;
+            acc.add(tile[idx], inv_n2, iv);
         }
-        res_block_partial<NT / 64>(acc, isum, a, ((size_t)z * st.B + b) * a.nblk + blockIdx.x);
+        res_block_partial<NT / 64>(acc, a, ((size_t)z * st.B + b) * a.nblk + blockIdx.x);
     } else {
         for (int idx = threadIdx.x; idx < np * C; idx += NT) {
             const int y = idx >> lc, c = idx & cm;
@@ -474,6 +474,7 @@ k_colpass_wave(DevState st, A a, FftPlan pl, const float2 *__restrict__ tw, int 
     const int np = st.np, r = st.r, nb = st.nb;
     const int x0 = blockIdx.x * C, b = blockIdx.y, z = kIsRes<A> ? blockIdx.z : 0;
     const StepArgs sa = res_led(a, z, np);
+    [[maybe_unused]] const float rg_led = res_gain<A>(st, sa.led, b);
     const int cs = min(C, np - x0);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     constexpr int LPC = 64 / CW;
@@ -527,19 +528,17 @@ k_colpass_wave(DevState st, A a, FftPlan pl, const float2 *__restrict__ tw, int 
     wave_transform<true, LPC>(cb, pl, stw, l);
     const float inv_n2 = 1.0f / ((float)np * (float)np);
     if constexpr (kIsRes<A>) {
-        float acc = 0.f;
-        unsigned isum = 0;
+        ResAcc<A> acc(rg_led);
 #pragma unroll
         for (int q = 0; q < NQY; ++q) {
             const int y = lane + 64 * q;
 #pragma unroll
             for (int c = 0; c < CW; ++c) {
                 if (y >= np || w * CW + c >= cs) continue;
-                acc = res_add(acc, wb[c * P + y], inv_n2, iv[q * CW + c]);
-                isum += iv[q * CW + c];
+                acc.add(wb[c * P + y], inv_n2, iv[q * CW + c]);
             }
         }
-        res_block_partial<NW>(acc, isum, a, ((size_t)z * st.B + b) * a.nblk + blockIdx.x);
+        res_block_partial<NW>(acc, a, ((size_t)z * st.B + b) * a.nblk + blockIdx.x);
     } else {
 #pragma unroll
         for (int q = 0; q < NQY; ++q) {
@@ -617,11 +616,13 @@ LdsLadder plan_lds_ladder(const FftPlan &pl, int np, int nb, int B, const Switch
 // the ladder's K1 / K2 for the update step (A = StepArgs) or the sweep (ResArgs)
 template <class A>
 static void pick_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols) {
-    rows = l.rows;
-    rows.fn = l.row_e == 16 ? (const void *)k_gather_rowifft_tiled<256, 16, A>
-              : l.row_e     ? (const void *)k_gather_rowifft_tiled<256, 24, A>
-                            : (const void *)k_gather_rowifft<A>;
-    rows.lds_static = l.row_e ? kLdsGatherRowifftTiled : kLdsGatherRowifft;
+    if constexpr (!kIsMom<A> && !kIsGainRes<A>) {  // the row kernels have no tail: every sweep launches the ResArgs ones
+        rows = l.rows;
+        rows.fn = l.row_e == 16 ? (const void *)k_gather_rowifft_tiled<256, 16, A>
+                  : l.row_e     ? (const void *)k_gather_rowifft_tiled<256, 24, A>
+                                : (const void *)k_gather_rowifft<A>;
+        rows.lds_static = l.row_e ? kLdsGatherRowifftTiled : kLdsGatherRowifft;
+    }
     cols = l.cols;
     const bool e16 = l.col_e == 16;
     if (l.cw) {
@@ -652,31 +653,38 @@ GeneralPlan plan_general_step(const DevState &st, GeneralPlan::Kind kind, const 
     p.ladder = l;
     pick_lds_kernels<StepArgs>(l, p.k1, p.k2);
     p.k3 = l.rows;
-    p.k3.fn = l.row_e == 16 ? (const void *)k_rowfft_update_tiled<256, 16>
-              : l.row_e     ? (const void *)k_rowfft_update_tiled<256, 24>
-                            : (const void *)k_rowfft_update;
+    p.k3.fn = l.row_e == 16 ? (const void *)k_rowfft_update_tiled<256, 16, false>
+              : l.row_e     ? (const void *)k_rowfft_update_tiled<256, 24, false>
+                            : (const void *)k_rowfft_update<false>;
     p.k3.lds_static = l.row_e ? kLdsRowfftUpdateTiled<256> : kLdsRowfftUpdate;
+    p.k3_gain = p.k3;
+    p.k3_gain.fn = l.row_e == 16 ? (const void *)k_rowfft_update_tiled<256, 16, true>
+                   : l.row_e     ? (const void *)k_rowfft_update_tiled<256, 24, true>
+                                 : (const void *)k_rowfft_update<true>;
     return p;
 }
 
-void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols) {
+void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols, StepKernel &cols_gain,
+                          StepKernel &cols_mom) {
+    pick_lds_kernels<GainResArgs>(l, rows, cols_gain);  // (rows untouched by these two)
+    pick_lds_kernels<MomArgs>(l, rows, cols_mom);
     pick_lds_kernels<ResArgs>(l, rows, cols);
 }
 
 hipError_t launch_general_step(const GeneralPlan &plan, const DevState &st, int led, int x0, int y0,
-                               const float2 *tw, bool first, hipStream_t s) {
+                               const float2 *tw, bool first, bool gains, hipStream_t s) {
     StepArgs sa;
     sa.led = led;
     sa.xc = x0 + st.np / 2;
     sa.yc = y0 + st.np / 2;
     if (plan.kind == GeneralPlan::Reg1024) {
-        const hipError_t e = launch_np1024_rows_cols(st, sa, tw, !first, s);
+        const hipError_t e = launch_np1024_rows_cols(st, sa, tw, !first, gains, s);
         if (e != hipSuccess) return e;
     } else if (plan.kind == GeneralPlan::Reg256) {
-        return launch_np256_rows_cols(st, sa, tw, !first, s);  // K4 inside, K5 folded
+        return launch_np256_rows_cols(st, sa, tw, !first, gains, s);  // K4 inside, K5 folded
     } else {
         // a refused launch would leave T stale under K4 / K5: the first error ends the step
-        for (const StepKernel *k : {&plan.k1, &plan.k2, &plan.k3}) {
+        for (const StepKernel *k : {&plan.k1, &plan.k2, gains ? &plan.k3_gain : &plan.k3}) {
             const hipError_t e = launch_step_kernel(*k, st, sa, plan.pl, tw, s);
             if (e != hipSuccess) return e;
         }

@@ -81,24 +81,26 @@ struct GeneralPlan {
     enum Kind { Reg1024, Reg256, Lds } kind;
     FftPlan pl;                               // of Np
     StepKernel k1, k2, k3;                    // Lds only
+    StepKernel k3_gain;                       // k3's GAIN instance: what a context with gains launches
     LdsLadder ladder;                         // Lds only: the rung k1-k3 were picked from
     // the register row / column kernels fold the pupil commit into the next
     // LED's row IDFT (launch_pupil_commit after the iteration's last LED)
     bool commit_folded() const { return kind != Lds; }
 };
 GeneralPlan plan_general_step(const DevState &st, GeneralPlan::Kind kind, const FftPlan &pl, const Switches &sw);
-// first: the iteration's first LED (register kernels: no pupil commit pending)
+// first: the iteration's first LED (register kernels: no pupil commit pending);
+// gains: some LED gain is not 1, the update kernels' GAIN instances
 hipError_t launch_general_step(const GeneralPlan &plan, const DevState &st, int led, int x0, int y0,
-                               const float2 *tw, bool first, hipStream_t s);
+                               const float2 *tw, bool first, bool gains, hipStream_t s);
 hipError_t launch_pupil_commit(const DevState &st, hipStream_t s);
 int pupil_parts(int nb);
 // Np 1024 / Np 256 register row/column kernels of the general path (np1024.hip, np256.hip)
 bool np1024_supported(int np, int r);
 bool np256_supported(int np, int r, int L, bool fp16);
 hipError_t launch_np1024_rows_cols(const DevState &st, const StepArgs &sa, const float2 *tw, bool commit,
-                                   hipStream_t s);
+                                   bool gains, hipStream_t s);
 hipError_t launch_np256_rows_cols(const DevState &st, const StepArgs &sa, const float2 *tw, bool commit,
-                                  hipStream_t s);
+                                  bool gains, hipStream_t s);
 
 // ---- the data-fidelity residual of the current state (residual.hip)
 // Scratch cap of a residual sweep: T of one launch's LEDs, [nl][B][nb][Np]
@@ -129,12 +131,25 @@ struct ResArgs {
     double *err, *ref;         // [n][B] the folded sums, by entry index
     int nblk;
 };
+// The same batch with another tail of the column kernels (residual_dev.hpp),
+// each a type of its own so the tail is chosen at compile time and the
+// ResArgs instances stay the code they were:
+//   GainResArgs  the residual under a gain table that is not all ones,
+//                E = sum (|psi| - g sqrt(I))^2 (fpm_set_gains)
+//   MomArgs      fpm_moments: perr / err hold Q = sum |psi|^2, pcross / cross
+//                C = sum |psi| sqrt(I) (null in a residual launch)
+struct GainResArgs : ResArgs {};
+struct MomArgs : ResArgs {
+    double *pcross, *cross;
+};
 // Which kernel pair a context's sweep launches and how many LEDs at a time;
 // decided with the rest of the context (plan_context: no HIP call).
 struct ResidualPlan {
     enum Kind { Reg256, Lds } kind;
     FftPlan pl;                // of Np
     StepKernel rows, cols;     // one LED's grid: the launch multiplies it by the batch
+    StepKernel cols_gain;      // cols with the gained residual's tail and with the moments' (fpm_moments):
+    StepKernel cols_mom;       //   the same launch shape
     LdsLadder ladder;          // Lds only: the rung rows / cols were picked from
     int nblk;                  // column blocks = partials per (LED, patch)
     int nl;                    // LEDs per launch
@@ -144,10 +159,13 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
                            const Switches &sw);
 // the sweep's kernels are the step's, instantiated for ResArgs: the ladder's
 // K1 / K2 (general.hip) and the Np 256 register column kernel (np256.hip)
-void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols);
-const void *residual_cols256_kernel();
-// rows, columns and fold of the nl entries ra.ent[ra.i0 ...]
-hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, const ResArgs &ra, int nl,
+enum class ResTail { Plain, Gain, Moments };
+void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols, StepKernel &cols_gain,
+                          StepKernel &cols_mom);
+const void *residual_cols256_kernel(ResTail tail);
+// rows, columns and fold of the nl entries ra.ent[ra.i0 ...] with the column
+// kernel of `tail` (Moments: ra.pcross / ra.cross set, both folds)
+hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, const MomArgs &ra, ResTail tail, int nl,
                                  const float2 *tw, hipStream_t s);
 
 // ---- batched transform of any length 2^a 3^b 5^c (fft_batch.hip)

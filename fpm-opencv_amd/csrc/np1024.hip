@@ -392,6 +392,7 @@ __global__ void __launch_bounds__(64 * CW) __attribute__((amdgpu_waves_per_eu(4)
 }
 
 // R2: grid (ceil(nb / WPB), B), block NT
+template <bool GAIN>
 __global__ void __launch_bounds__(n1k::NT) k_rows1024_fwd(DevState st, StepArgs sa, const float2 *__restrict__ tw) {
     using namespace n1k;
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
@@ -404,6 +405,7 @@ __global__ void __launch_bounds__(n1k::NT) k_rows1024_fwd(DevState st, StepArgs 
     const float2 *twL = sm;
     float2 *wt = sm + N + w * WTILE;
     const int r = st.r, nb = st.nb, b = blockIdx.y, row = blockIdx.x * WPB + w;
+    const float gl = fused_gain<GAIN>(st, sa.led, b);
     // the row's T first (its memory latency runs under the max|P| reduction
     // below), then max|P| of the previous commit from its npart partial
     // maxima (:415) -- every load of both issued before the first use (the
@@ -494,7 +496,7 @@ __global__ void __launch_bounds__(n1k::NT) k_rows1024_fwd(DevState st, StepArgs 
             if (kx * kx > w2) continue;
             const size_t si = srow + kx;
             float2 num;
-            spec_st(st, b, si, general_update(x[4 * p + bb], ov[i], pv[i], pm, st, num));
+            spec_st(st, b, si, general_update<GAIN>(x[4 * p + bb], ov[i], pv[i], pm, gl, st, num));
             dP[kx] = num;
         }
     }
@@ -507,7 +509,7 @@ __global__ void __launch_bounds__(n1k::NT) k_rows1024_fwd(DevState st, StepArgs 
 bool np1024_supported(int np, int r) { return np == n1k::N && r >= 1 && r < n1k::H; }
 
 hipError_t launch_np1024_rows_cols(const DevState &st, const StepArgs &sa, const float2 *tw, bool commit,
-                                   hipStream_t s) {
+                                   bool gains, hipStream_t s) {
     using namespace n1k;
     if (!np1024_supported(st.np, st.r) || st.meas_g != N || st.npart < st.nb) return hipErrorInvalidValue;
     const size_t lds_r = (size_t)(N + WPB * WTILE) * sizeof(float2);
@@ -522,7 +524,8 @@ hipError_t launch_np1024_rows_cols(const DevState &st, const StepArgs &sa, const
     const dim3 rgrid((st.nb + WPB - 1) / WPB, st.B);
     hipLaunchKernelGGL(k_rows1024_inv, rgrid, dim3(NT), lds_r, s, st, sa, tw, commit ? 1 : 0);
     hipLaunchKernelGGL(k_cols1024<cw>, dim3(N / cw, st.B), dim3(64 * cw), lds_c, s, st, sa, tw);
-    hipLaunchKernelGGL(k_rows1024_fwd, rgrid, dim3(NT), lds_r, s, st, sa, tw);
+    if (gains) hipLaunchKernelGGL(k_rows1024_fwd<true>, rgrid, dim3(NT), lds_r, s, st, sa, tw);
+    else hipLaunchKernelGGL(k_rows1024_fwd<false>, rgrid, dim3(NT), lds_r, s, st, sa, tw);
     return hipGetLastError();
 }
 

@@ -161,6 +161,7 @@ __global__ void __launch_bounds__(n256::NT) k_cols256(DevState st, A a, const fl
         if (!xcd_block(N / GPB, st.B, b, sub)) return;  // block-uniform
     }
     const StepArgs sa = res_led(a, z, N);
+    [[maybe_unused]] const float rg_led = res_gain<A>(st, sa.led, b);
     const int x0 = sub * GPB;
     const float2 twv = tw[threadIdx.x];
     float2 *twL = sm;
@@ -201,15 +202,13 @@ __global__ void __launch_bounds__(n256::NT) k_cols256(DevState st, A a, const fl
     const unsigned iw[8] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w};
     if constexpr (kIsRes<A>) {
         const float inv_n2 = 1.0f / ((float)N * (float)N);
-        float acc = 0.f;
-        unsigned isum = 0;
+        ResAcc<A> acc(rg_led);
 #pragma unroll
         for (int m = 0; m < 16; ++m) {
             const unsigned iv = (iw[m >> 1] >> (16 * (m & 1))) & 0xffffu;
-            acc = res_add(acc, y[m], inv_n2, iv);
-            isum += iv;
+            acc.add(y[m], inv_n2, iv);
         }
-        res_block_partial<WPB>(acc, isum, a, ((size_t)z * st.B + b) * a.nblk + sub);
+        res_block_partial<WPB>(acc, a, ((size_t)z * st.B + b) * a.nblk + sub);
     } else {
         // amplitude replacement (:378-394), np1024.hip's form: with y the unscaled
         // IDFT value, psi = y / N^2 and sqrt(I) psi / |psi + eps (1 + i)| =
@@ -241,6 +240,7 @@ __global__ void __launch_bounds__(n256::NT) k_cols256(DevState st, A a, const fl
 // row's window tiles and writes their maxima and the tile row's maximum --
 // general.hip K4's values, bit for bit, without its launch.
 constexpr int kMaxWinTiles = (2 * (n256::H - 1) + 15) / kTile + 1;  // tile columns a window spans, r < 128
+template <bool GAIN>
 __global__ void __launch_bounds__(n256::NT) __attribute__((amdgpu_waves_per_eu(4))) k_rows256_fwd(DevState st, StepArgs sa, const float2 *__restrict__ tw) {
     using namespace n256;
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
@@ -253,6 +253,7 @@ __global__ void __launch_bounds__(n256::NT) __attribute__((amdgpu_waves_per_eu(4
     if (!xcd_block((2 * r + 15) / kTile + 1, st.B, b, sub)) return;  // block-uniform
     const int ty = ty0 + sub;
     if (ty > ty1) return;  // block-uniform, before any barrier
+    const float gl = fused_gain<GAIN>(st, sa.led, b);
     const int row = ty * kTile + g - (sa.yc - r);  // box row of this group's spectrum row
     const bool act = row >= 0 && row < nb;
     // the tile row's maxima outside the window: unchanged by this launch,
@@ -310,7 +311,7 @@ __global__ void __launch_bounds__(n256::NT) __attribute__((amdgpu_waves_per_eu(4
                 // numerator instead of between the two, this kernel schedules one instruction more
                 const float2 o = ov[k];                                 // pre-update Objfcrop (:361)
                 const float2 p = pp[k];
-                const float2 D = csub(F[8 * hp + k], cmul(o, p));       // Objfup - ObjfcropP (:409,463)
+                const float2 D = csub(GAIN ? cscale(F[8 * hp + k], gl) : F[8 * hp + k], cmul(o, p));      // Objfup - ObjfcropP (:409,463)
                 const float pa = cmag(p);                               // object update (:406-419,433)
                 const float2 dpc = cmul(cmul(D, cscale(cconj(p), pa)), upd_coef_div(pa * pa + st.delta2, st.d2_im, pm));
                 sp[kx] = cadd(o, dpc);
@@ -362,7 +363,11 @@ __global__ void __launch_bounds__(n256::NT) __attribute__((amdgpu_waves_per_eu(4
 
 }  // namespace
 
-const void *residual_cols256_kernel() { return (const void *)k_cols256<ResArgs>; }
+const void *residual_cols256_kernel(ResTail tail) {
+    return tail == ResTail::Moments ? (const void *)k_cols256<MomArgs>
+           : tail == ResTail::Gain  ? (const void *)k_cols256<GainResArgs>
+                                    : (const void *)k_cols256<ResArgs>;
+}
 
 // Register path for this context?  Np 256, fp32 spectrum, r < 128 (every box
 // row's frequencies inside one 256-point period), the stack in the fused
@@ -372,7 +377,7 @@ bool np256_supported(int np, int r, int L, bool fp16) {
 }
 
 hipError_t launch_np256_rows_cols(const DevState &st, const StepArgs &sa, const float2 *tw, bool commit,
-                                  hipStream_t s) {
+                                  bool gains, hipStream_t s) {
     using namespace n256;
     if (!np256_supported(st.np, st.r, st.L, st.spec16 != nullptr) || st.meas_g != 16 || st.npart < st.nb ||
         st.npart > NT || !st.T || !st.spec)
@@ -382,7 +387,8 @@ hipError_t launch_np256_rows_cols(const DevState &st, const StepArgs &sa, const 
     hipLaunchKernelGGL(k_rows256_inv, dim3(row_blocks(st.nb) * Bp), dim3(NT), lds_r, s, st, sa, tw, commit ? 1 : 0);
     hipLaunchKernelGGL(k_cols256<StepArgs>, dim3(kColBlocks * Bp), dim3(NT), lds_cols(st.nb), s, st, sa, tw);
     const int ntr = (2 * st.r + 15) / kTile + 1;  // tile rows a window can span
-    hipLaunchKernelGGL(k_rows256_fwd, dim3(ntr * Bp), dim3(NT), lds_r, s, st, sa, tw);
+    if (gains) hipLaunchKernelGGL(k_rows256_fwd<true>, dim3(ntr * Bp), dim3(NT), lds_r, s, st, sa, tw);
+    else hipLaunchKernelGGL(k_rows256_fwd<false>, dim3(ntr * Bp), dim3(NT), lds_r, s, st, sa, tw);
     return hipGetLastError();
 }
 

@@ -17,6 +17,12 @@
 // spectrum, the pupil and the stack, and write only the context's residual
 // scratch.
 //
+// The column kernels have three tails (residual_dev.hpp): ResArgs, the sums
+// above; GainResArgs, E under the LED gains, E = sum (|psi| - g sqrt(I))^2,
+// launched when some gain is not 1 (fpm_set_gains); MomArgs, the raw moments
+// Q = sum |psi|^2 and C = sum |psi| sqrt(I) beside S (fpm_moments).  One launch
+// shape, one row kernel and one fold serve all three.
+//
 // What is left in this file:
 //   k_res_rows256   the register pair's row kernel (Np 256, fp32 spectrum, the
 //                   stack in the g = 16 column layout): np256.hip's R1 without
@@ -97,7 +103,7 @@ __global__ void __launch_bounds__(n256::NT) k_res_rows256(DevState st, ResArgs r
 
 // ---- fold ----------------------------------------------------------------------
 // a thread per (LED of the batch, patch): its nblk partials in index order
-__global__ void __launch_bounds__(256) k_res_fold(ResArgs ra, int nl, int B) {
+__global__ void __launch_bounds__(256) k_res_fold(MomArgs ra, int nl, int B) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= nl * B) return;
     const double *pe = ra.perr + (size_t)i * ra.nblk;
@@ -109,6 +115,12 @@ __global__ void __launch_bounds__(256) k_res_fold(ResArgs ra, int nl, int B) {
         s += pr[k];
     }
     const size_t o = (size_t)ra.i0 * B + i;  // [n][B], by entry index
+    if (ra.pcross) {  // fpm_moments: the cross sums the same way
+        const double *pc = ra.pcross + (size_t)i * ra.nblk;
+        double c = 0.0;
+        for (int k = 0; k < ra.nblk; ++k) c += pc[k];
+        ra.cross[o] = c;
+    }
     ra.err[o] = e;
     ra.ref[o] = (double)s;  // exact: S < 2^16 Np^2 < 2^53
 }
@@ -130,11 +142,14 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
     if (p.kind == ResidualPlan::Reg256) {
         const int Bp = xcd_patches(B);
         p.rows = StepKernel{(const void *)k_res_rows256, dim3(row_blocks(nb) * Bp), dim3(NT), lds_rows(), 0};
-        p.cols = StepKernel{residual_cols256_kernel(), dim3(kColBlocks * Bp), dim3(NT), lds_cols(nb), 0};
+        p.cols = StepKernel{residual_cols256_kernel(ResTail::Plain), dim3(kColBlocks * Bp), dim3(NT), lds_cols(nb), 0};
+        p.cols_gain = p.cols_mom = p.cols;
+        p.cols_gain.fn = residual_cols256_kernel(ResTail::Gain);
+        p.cols_mom.fn = residual_cols256_kernel(ResTail::Moments);
         p.nblk = kColBlocks;
     } else {
         p.ladder = plan_lds_ladder(pl, np, nb, B, sw, false);
-        residual_lds_kernels(p.ladder, p.rows, p.cols);
+        residual_lds_kernels(p.ladder, p.rows, p.cols, p.cols_gain, p.cols_mom);
         p.nblk = (int)p.cols.grid.x;
     }
     // LEDs per launch: as many as the scratch cap holds (FPM_RES_BATCH=n forces n)
@@ -145,18 +160,22 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
     return p;
 }
 
-hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, const ResArgs &ra_in, int nl,
+hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, const MomArgs &ra_in, ResTail tail, int nl,
                                  const float2 *tw, hipStream_t s) {
-    ResArgs ra = ra_in;
+    MomArgs ra = ra_in;
     ra.nblk = p.nblk;
-    for (const StepKernel *k : {&p.rows, &p.cols}) {
+    const StepKernel *cols = tail == ResTail::Moments ? &p.cols_mom : tail == ResTail::Gain ? &p.cols_gain : &p.cols;
+    for (const StepKernel *k : {&p.rows, cols}) {
+        // every instance but the moments' takes the ResArgs base (the leading bytes of ra)
+        const bool mom = k == &p.cols_mom;
         hipError_t e;
         if (p.kind == ResidualPlan::Reg256) {  // the register kernels take no FftPlan
             DevState sv = st;
             void *args[] = {&sv, &ra, &tw};
             e = hipLaunchKernel(k->fn, dim3(k->grid.x * nl), k->block, args, k->lds, s);
         } else {
-            e = launch_step_kernel(*k, st, ra, p.pl, tw, s, nl);
+            e = mom ? launch_step_kernel(*k, st, ra, p.pl, tw, s, nl)
+                    : launch_step_kernel(*k, st, static_cast<const ResArgs &>(ra), p.pl, tw, s, nl);
         }
         if (e != hipSuccess) return e;
     }

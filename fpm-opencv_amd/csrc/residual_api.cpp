@@ -1,11 +1,14 @@
-// residual_api.cpp -- fpm_residual and fpm_residual_at: the data-fidelity
-// residual of the current state (residual.hip) as a sequence of steps: refuse
+// residual_api.cpp -- fpm_residual, fpm_residual_at and fpm_moments: the
+// data-fidelity residual of the current state, or the raw moments it is made
+// of (residual.hip), as a sequence of steps: refuse
 // a capturing stream, make sure the scratch exists, launch the batches of an
 // entry list between two events, copy the folded sums out, report the event
 // time.  One path: fpm_residual sweeps the context's identity list (every
 // position of order[] with its own window), fpm_residual_at a list the caller
 // gives as (position, offset) probes, resolved and validated on the host and
 // run in pieces of at most n_order entries, the size of the folded-sum scratch.
+// fpm_moments is the same path with the column kernels' moments tail and one
+// more pair of sum buffers; it takes either list.
 // Read-only: nothing of the state, the stack or the last run's timing and
 // clock is written.
 // (The kernels' file is residual.hip; the two cannot share a basename, Makefile.)
@@ -38,34 +41,52 @@ int ensure_scratch(fpm_ctx *c) {
     if (rc) return rc;
     for (auto &e : c->res_ev)
         if (!e) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(allow_large_lds({&p.rows, &p.cols}, c->lds_limit));  // Np 1024 and up, tiled columns
+    HIP_TRY(allow_large_lds({&p.rows, &p.cols, &p.cols_gain}, c->lds_limit));  // Np 1024 and up, tiled columns
     c->res_ready = true;
     return FPM_OK;
 }
 
-// the entries ent[0, n) (device, n <= n_order) in list order, nl per launch
-int launch_entries(fpm_ctx *c, const ResEntry *ent, int n) {
+// fpm_moments' additions to it, by its first call
+int ensure_moments_scratch(fpm_ctx *c) {
+    int rc = ensure_scratch(c);
+    if (rc || c->mom_ready) return rc;
     const ResidualPlan &p = c->rplan;
-    ResArgs ra{ent, 0, c->res_T, c->res_perr, c->res_pref, c->res_err, c->res_ref, p.nblk};
+    if (!c->res_pcross) rc = dalloc(c, &c->res_pcross, (size_t)p.nl * c->st.B * p.nblk, false);
+    if (!rc && !c->res_cross) rc = dalloc(c, &c->res_cross, (size_t)c->prob.n_order * c->st.B, false);
+    if (rc) return rc;
+    HIP_TRY(allow_large_lds({&p.cols_mom}, c->lds_limit));
+    c->mom_ready = true;
+    return FPM_OK;
+}
+
+// the entries ent[0, n) (device, n <= n_order) in list order, nl per launch;
+// mom: the moments (Q in the err buffers, C in the cross ones)
+int launch_entries(fpm_ctx *c, const ResEntry *ent, int n, bool mom) {
+    const ResidualPlan &p = c->rplan;
+    MomArgs ra{{ent, 0, c->res_T, c->res_perr, c->res_pref, c->res_err, c->res_ref, p.nblk},
+               mom ? c->res_pcross : nullptr, mom ? c->res_cross : nullptr};
+    // a context whose gains are all ones launches the residual's ungained instance
+    const ResTail tail = mom ? ResTail::Moments : c->gains_unit ? ResTail::Plain : ResTail::Gain;
     for (int i0 = 0; i0 < n; i0 += p.nl) {
         ra.i0 = i0;
-        HIP_TRY(launch_residual_batch(p, c->st, ra, std::min(p.nl, n - i0), c->tw_np, c->stream));
+        HIP_TRY(launch_residual_batch(p, c->st, ra, tail, std::min(p.nl, n - i0), c->tw_np, c->stream));
     }
     return FPM_OK;
 }
 
-// their folded sums [n][B] to err / ref (either may be null)
-int copy_sums(fpm_ctx *c, int n, double *err, double *ref) {
+// their folded sums [n][B] to err / ref / cross (any may be null)
+int copy_sums(fpm_ctx *c, int n, double *err, double *ref, double *cross = nullptr) {
     const size_t bytes = (size_t)n * c->st.B * sizeof(double);
     if (err) HIP_TRY(hipMemcpyAsync(err, c->res_err, bytes, hipMemcpyDeviceToHost, c->stream));
     if (ref) HIP_TRY(hipMemcpyAsync(ref, c->res_ref, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (cross) HIP_TRY(hipMemcpyAsync(cross, c->res_cross, bytes, hipMemcpyDeviceToHost, c->stream));
     return FPM_OK;
 }
 
-// what both entry points check before anything is enqueued
-int admit(fpm_ctx *c, const char *what, const double *err, const double *ref) {
+// what every entry point checks before anything is enqueued
+int admit(fpm_ctx *c, const char *what, bool any_output) {
     if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
-    if (!err && !ref) return set_err(FPM_ERR_INVAL, "%s: err and ref are both NULL", what);
+    if (!any_output) return set_err(FPM_ERR_INVAL, "%s: every output pointer is NULL", what);
     if (!c->initialized) return set_err(FPM_ERR_STATE, "%s before fpm_init", what);
     HIP_TRY(hipSetDevice(c->device));
     return refuse_capture(c, what);
@@ -81,39 +102,38 @@ int finish(fpm_ctx *c, double *elapsed_ms) {
     return FPM_OK;
 }
 
-}  // namespace
-
-extern "C" int fpm_residual(fpm_ctx *c, double *err, double *ref, double *elapsed_ms) {
-    int rc = admit(c, "fpm_residual", err, ref);
-    if (rc || (rc = ensure_scratch(c))) return rc;
+// the context's identity list: every position of order[] with its own window
+int sweep_identity(fpm_ctx *c, bool mom, double *err, double *ref, double *cross, double *elapsed_ms) {
+    int rc = mom ? ensure_moments_scratch(c) : ensure_scratch(c);
+    if (rc) return rc;
     const int n = c->prob.n_order;
     HIP_TRY(hipEventRecord(c->res_ev[0], c->stream));
-    if ((rc = launch_entries(c, c->ident_dev, n))) return rc;
+    if ((rc = launch_entries(c, c->ident_dev, n, mom))) return rc;
     HIP_TRY(hipEventRecord(c->res_ev[1], c->stream));
-    if ((rc = copy_sums(c, n, err, ref))) return rc;
+    if ((rc = copy_sums(c, n, err, ref, cross))) return rc;
     return finish(c, elapsed_ms);
 }
 
-extern "C" int fpm_residual_at(fpm_ctx *c, const fpm_probe *probes, int n, double *err, double *ref,
-                               double *elapsed_ms) {
-    int rc = admit(c, "fpm_residual_at", err, ref);
-    if (rc) return rc;
-    if (!probes || n < 1) return set_err(FPM_ERR_INVAL, "fpm_residual_at: %s", probes ? "n < 1" : "null probes");
+// a probe list, after admit
+int sweep_probes(fpm_ctx *c, const char *what, bool mom, const fpm_probe *probes, int n, double *err, double *ref,
+                 double *cross, double *elapsed_ms) {
+    int rc;
+    if (!probes || n < 1) return set_err(FPM_ERR_INVAL, "%s: %s", what, probes ? "n < 1" : "null probes");
     // every entry resolved and validated before the first launch
     const int np = c->st.np, L = c->st.L, n_order = c->prob.n_order;
     std::vector<ResEntry> ent((size_t)n);
     for (int k = 0; k < n; ++k) {
         const fpm_probe &q = probes[k];
         if (q.pos < 0 || q.pos >= n_order)
-            return set_err(FPM_ERR_INVAL, "fpm_residual_at: entry %d: pos=%d outside order[0, %d)", k, q.pos, n_order);
+            return set_err(FPM_ERR_INVAL, "%s: entry %d: pos=%d outside order[0, %d)", what, k, q.pos, n_order);
         const int led = c->order[q.pos];
         const long long x = (long long)c->x0[led] + q.dx, y = (long long)c->y0[led] + q.dy;
         if (x < 0 || x > L - np || y < 0 || y > L - np)
-            return set_err(FPM_ERR_INVAL, "fpm_residual_at: entry %d: window (%lld,%lld) of LED %d leaves the %dx%d "
-                           "spectrum", k, x, y, led, L, L);
+            return set_err(FPM_ERR_INVAL, "%s: entry %d: window (%lld,%lld) of LED %d leaves the %dx%d "
+                           "spectrum", what, k, x, y, led, L, L);
         ent[k] = ResEntry{led, (int)x + np / 2, (int)y + np / 2, 0};
     }
-    if ((rc = ensure_scratch(c))) return rc;
+    if ((rc = mom ? ensure_moments_scratch(c) : ensure_scratch(c))) return rc;
     const size_t B = c->st.B;
     HIP_TRY(hipEventRecord(c->res_ev[0], c->stream));
     // pieces of n_order entries, what the entry table and the folded sums
@@ -124,10 +144,32 @@ extern "C" int fpm_residual_at(fpm_ctx *c, const fpm_probe *probes, int n, doubl
         const int m = std::min(n_order, n - k0);
         HIP_TRY(hipMemcpyAsync(c->res_ent, ent.data() + k0, (size_t)m * sizeof(ResEntry), hipMemcpyHostToDevice,
                                c->stream));
-        if ((rc = launch_entries(c, c->res_ent, m)) ||
-            (rc = copy_sums(c, m, err ? err + k0 * B : nullptr, ref ? ref + k0 * B : nullptr)))
+        if ((rc = launch_entries(c, c->res_ent, m, mom)) ||
+            (rc = copy_sums(c, m, err ? err + k0 * B : nullptr, ref ? ref + k0 * B : nullptr,
+                            cross ? cross + k0 * B : nullptr)))
             return rc;
     }
     HIP_TRY(hipEventRecord(c->res_ev[1], c->stream));
     return finish(c, elapsed_ms);
+}
+
+}  // namespace
+
+extern "C" int fpm_residual(fpm_ctx *c, double *err, double *ref, double *elapsed_ms) {
+    const int rc = admit(c, "fpm_residual", err || ref);
+    return rc ? rc : sweep_identity(c, false, err, ref, nullptr, elapsed_ms);
+}
+
+extern "C" int fpm_residual_at(fpm_ctx *c, const fpm_probe *probes, int n, double *err, double *ref,
+                               double *elapsed_ms) {
+    const int rc = admit(c, "fpm_residual_at", err || ref);
+    return rc ? rc : sweep_probes(c, "fpm_residual_at", false, probes, n, err, ref, nullptr, elapsed_ms);
+}
+
+extern "C" int fpm_moments(fpm_ctx *c, const fpm_probe *probes, int n, double *model, double *cross, double *ref,
+                           double *elapsed_ms) {
+    const int rc = admit(c, "fpm_moments", model || cross || ref);
+    if (rc) return rc;
+    return probes ? sweep_probes(c, "fpm_moments", true, probes, n, model, ref, cross, elapsed_ms)
+                  : sweep_identity(c, true, model, ref, cross, elapsed_ms);
 }

@@ -15,8 +15,17 @@
 
 namespace fpm {
 
+// GainResArgs and MomArgs (launch.hpp) are the same batch with another tail:
+// the squared difference under the LED's gain, and the raw moments
+// sum |psi|^2 and sum |psi| sqrt(I) (fpm_moments).  Everything before the tail
+// is the ResArgs instance's, and the ResArgs instance -- what a context
+// without gains launches -- has the tail it always had.
 template <class A>
-constexpr bool kIsRes = std::is_same<A, ResArgs>::value;
+constexpr bool kIsMom = std::is_same<A, MomArgs>::value;
+template <class A>
+constexpr bool kIsGainRes = std::is_same<A, GainResArgs>::value;
+template <class A>
+constexpr bool kIsRes = std::is_same<A, ResArgs>::value || kIsGainRes<A> || kIsMom<A>;
 
 // (|psi| - sqrt(I))^2 of one pixel added to acc: v = the unscaled IDFT value,
 // psi = v / Np^2 (the reference's ifft2 scaling), no eps.  I is exact and
@@ -30,11 +39,62 @@ __device__ __forceinline__ float res_add(float acc, float2 v, float inv_n2, unsi
     const float d = a - s;
     return acc + (2.0f * a < s ? __builtin_fmaf(a, a - 2.0f * s, fi) : d * d);
 }
+// The same under the LED's gain g (g2 = g g): (|psi| - g sqrt(I))^2, expanded
+// around g2 I where |psi| < g sqrt(I) / 2.  With g = 1.0f both products are
+// exact and the value is res_add's to the bit: the empty asm keeps the two
+// products opaque, so nothing below fuses them into a multiply-add and the
+// rest is res_add's own expression, contracted as the compiler contracts that
+// (fused, the Np 90 / 200 / 2700 sweeps rounded differently from res_add).
+__device__ __forceinline__ float res_add_gain(float acc, float2 v, float inv_n2, unsigned I, float g, float g2) {
+    const float a = sqrtf(cabs2(v)) * inv_n2, fi = (float)I;
+    float s = g * sqrtf(fi), gi = g2 * fi;
+    asm("" : "+v"(s), "+v"(gi));
+    const float d = a - s;
+    return acc + (2.0f * a < s ? __builtin_fmaf(a, a - 2.0f * s, gi) : d * d);
+}
+
+// A lane's sums over its pixels, the tail of every column kernel's sweep
+// instance.  ResArgs: e = sum (|psi| - sqrt(I))^2; GainResArgs: the same under
+// the LED's gain.  MomArgs: q = sum |psi|^2 and c = sum |psi| sqrt(I), each
+// product formed in fp32 and accumulated as e is; raw, the gain table does not
+// enter.  s = sum I as an integer in all three.
+// The gain a column kernel's tail needs, loaded at the top of the kernel (the
+// scalar load's latency runs under the column transform): the LED's for the
+// gained residual, none for the ungained one, the update step (its gain enters
+// at the update) or the moments.
+template <class A>
+__device__ __forceinline__ float res_gain(const DevState &st, int led, int b) {
+    if constexpr (kIsGainRes<A>) return led_gain(st, led, b);
+    else return 1.0f;
+}
+template <class A>
+struct ResAcc {
+    float e = 0.f, g, g2;
+    unsigned s = 0;
+    __device__ __forceinline__ explicit ResAcc(float gain) : g(gain), g2(gain * gain) {}
+    __device__ __forceinline__ void add(float2 v, float inv_n2, unsigned I) {
+        if constexpr (kIsGainRes<A>) e = res_add_gain(e, v, inv_n2, I, g, g2);
+        else e = res_add(e, v, inv_n2, I);
+        s += I;
+    }
+};
+template <>
+struct ResAcc<MomArgs> {
+    float q = 0.f, c = 0.f;
+    unsigned s = 0;
+    __device__ __forceinline__ explicit ResAcc(float) {}
+    __device__ __forceinline__ void add(float2 v, float inv_n2, unsigned I) {
+        const float a = sqrtf(cabs2(v)) * inv_n2;
+        q += a * a;
+        c += a * sqrtf((float)I);
+        s += I;
+    }
+};
 
 // The LED a block works on: the step's own, or entry i0 + z of the batch's
 // list (stack index and centre of its window, launch.hpp ResEntry) in one load
 __device__ __forceinline__ StepArgs res_led(const StepArgs &sa, int, int) { return sa; }
-__device__ __forceinline__ StepArgs res_led(const ResArgs &ra, int z, int) {
+__device__ __forceinline__ StepArgs res_led(const ResArgs &ra, int z, int) {  // (a MomArgs is a ResArgs)
     const int4 e = *reinterpret_cast<const int4 *>(ra.ent + ra.i0 + z);
     StepArgs sa;
     sa.led = e.x;
@@ -54,20 +114,29 @@ __device__ __forceinline__ float2 *res_T(const DevState &st, const ResArgs &ra, 
 
 // The block's sums as one partial: lanes -> wave in double / u64 (xor
 // butterfly, a fixed association), waves -> block in wave order by thread 0.
-// Every thread of the block must call it.  kResPartialLds: its __shared__ bytes.
+// Every thread of the block must call it.  kResPartialLds: its __shared__ bytes,
+// the same for both tails (the moments' second sum goes through the same
+// arrays after a barrier), so one launch shape serves both instances.
 template <int NW>
 constexpr size_t kResPartialLds = NW * (sizeof(double) + sizeof(unsigned long long));
-template <int NW>
-__device__ __forceinline__ void res_block_partial(float acc, unsigned isum, const ResArgs &ra, size_t slot) {
+template <int NW, class A>
+__device__ __forceinline__ void res_block_partial(const ResAcc<A> &acc, const A &ra, size_t slot) {
     __shared__ double dred[NW];
     __shared__ unsigned long long ured[NW];
     static_assert(sizeof dred + sizeof ured == kResPartialLds<NW>, "the create-time LDS check counts these arrays");
-    double d = (double)acc;
-    unsigned long long u = isum;
+    double d, d2 = 0.0;
+    if constexpr (kIsMom<A>) {
+        d = (double)acc.q;
+        d2 = (double)acc.c;
+    } else {
+        d = (double)acc.e;
+    }
+    unsigned long long u = acc.s;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         d += __shfl_xor(d, o);
         u += __shfl_xor(u, o);
+        if constexpr (kIsMom<A>) d2 += __shfl_xor(d2, o);
     }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     if (lane == 0) {
@@ -82,6 +151,15 @@ __device__ __forceinline__ void res_block_partial(float acc, unsigned isum, cons
         }
         ra.perr[slot] = d;
         ra.pref[slot] = u;
+    }
+    if constexpr (kIsMom<A>) {  // the cross sums, same order, through dred again
+        __syncthreads();
+        if (lane == 0) dred[w] = d2;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int i = 1; i < NW; ++i) d2 += dred[i];
+            ra.pcross[slot] = d2;
+        }
     }
 }
 

@@ -56,7 +56,7 @@ hipError_t launch_led_chains(const fpm_ctx *c, int g0, int g1, hipStream_t s) {
         const int led = c->order[i];
         for (int g = g0; g < g1; ++g)
             HIP_RET(launch_general_step(c->gplan[g], view[g], led, c->x0[led], c->y0[led], c->tw_np, i == 0,
-                                        group_stream(c, g, s)));
+                                        !c->gains_unit, group_stream(c, g, s)));
     }
     // Np 1024 / 256 register kernels: the last LED's pupil commit (the others
     // are folded into the next LED's row IDFT)
@@ -234,7 +234,8 @@ int fpm_run(fpm_ctx *c, int iters) {
     if (use_graph && (rc = general_graph(c))) return rc;
     const bool last_only = (c->prob.flags & FPM_FLAG_OBJCROP_LAST_ONLY) != 0;
     const FusedLaunch in{c->meas, c->order_dev, c->x0_dev, c->y0_dev, c->prob.n_order, c->tw_np, c->dbg,
-                         c->kernel == Kernel::Np90 ? c->sw.s90_dense : c->sw.mr_dense, c->sw.no_ledtab};
+                         c->kernel == Kernel::Np90 ? c->sw.s90_dense : c->sw.mr_dense, c->sw.no_ledtab,
+                         !c->gains_unit};
     const hipEvent_t *ev = c->evpool.data();
     HIP_TRY(hipEventRecord(ev[0], c->stream));
     for (int it = 0; it < iters; ++it) {

@@ -25,13 +25,23 @@ namespace fpm {
 // (four in a row measured slower).  Every fused kernel
 // calls this one function; tests/test_gpu_update_coef.py pins it through
 // fpm_debug_slot_update up to |O|^2 + delta1 = 1e30.
-__device__ __forceinline__ float2 slot_update(float2 f, float2 o, float2 p, float pm, const DevState &st,
+// GAIN, g: the LED's gain (fused_gain): the measured amplitude is g sqrt(I),
+// and the transform after the amplitude replacement is linear, so Objfup = g f
+// and D = g f - ObjfcropP, one packed multiply-add in place of the subtraction
+// (g = 1.0f: g f is exact, the same bits).  Compile time, because the scalar
+// costs the fused kernels registers they do not have (DESIGN.md section 4.6:
+// 0.3 - 3.5 % of a launch): a context whose gains are all ones launches the
+// GAIN = false instances, which are the kernels as they were.
+template <bool GAIN>
+__device__ __forceinline__ float2 slot_update(float2 f, float2 o, float2 p, float pm, float g, const DevState &st,
                                               float2 &num, float &oa) {
     const pf2 po = pin(o), pp = pin(p);
     const float pa2 = cabs2(p), oa2 = cabs2(o);
     const float pa = __builtin_amdgcn_sqrtf(pa2);
     oa = __builtin_amdgcn_sqrtf(oa2);
-    const pf2 D = pin(f) - pmul(po, pp);
+    pf2 D;
+    if constexpr (GAIN) D = pin(f) * g - pmul(po, pp);
+    else D = pin(f) - pmul(po, pp);
     const float ap = __builtin_fmaf(pa, pa, st.delta2), ao = __builtin_fmaf(oa, oa, st.delta1);
     const float rp = __builtin_amdgcn_rcpf(ap), ro = __builtin_amdgcn_rcpf(ao);
     const pf2 dp = pmulc(D, pp), dq = pmulc(D, po);
@@ -46,10 +56,13 @@ __device__ __forceinline__ float2 slot_update(float2 f, float2 o, float2 p, floa
 
 // The same update in the general path (general.hip, np1024.hip, np256.hip),
 // with IEEE divisions (upd_coef_div): F = Objfup (:394), o = the pre-update
-// Objfcrop (:361).  Returns O', writes the pupil numerator to num.
-__device__ __forceinline__ float2 general_update(float2 F, float2 o, float2 p, float pm, const DevState &st,
+// Objfcrop (:361); GAIN, g: the LED's gain (Objfup = g F, as in slot_update: a
+// compile-time variant here too, config 5 measured 0.2 % either side of the
+// parent with the factor at run time).  Returns O', writes the pupil numerator to num.
+template <bool GAIN>
+__device__ __forceinline__ float2 general_update(float2 F, float2 o, float2 p, float pm, float g, const DevState &st,
                                                  float2 &num) {
-    const float2 D = csub(F, cmul(o, p));  // Objfup - ObjfcropP (:409,463)
+    const float2 D = csub(GAIN ? cscale(F, g) : F, cmul(o, p));  // Objfup - ObjfcropP (:409,463)
     // object update (:406-419,433): D |P| P* / ((|P|^2 + d2) max|P|)
     const float pa = cmag(p);
     const float2 dpc = cmul(cmul(D, cscale(cconj(p), pa)), upd_coef_div(pa * pa + st.delta2, st.d2_im, pm));

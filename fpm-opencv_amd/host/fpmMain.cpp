@@ -51,6 +51,20 @@
 //                      crop_y0 as used last, probe_ms.  Works with --grid and
 //                      --residual (the sweep then follows the iteration and
 //                      precedes the search)
+//   --calibrate-gains  LED brightness calibration: after every iteration but the
+//                      last, one gain step.  fpm_moments gives Q = sum |psi|^2,
+//                      C = sum |psi| sqrt(I) and S = sum I of the current state
+//                      per (LED, patch); the image's amplitude factor becomes
+//                      g = C / S (unchanged where S = 0), each patch's factors
+//                      are scaled to an S-weighted mean of g^2 of 1 (gain and
+//                      object share a scale), clipped to [0.25, 4] and installed
+//                      with fpm_set_gains: the solver then uses g sqrt(I)
+//                      wherever it used sqrt(I).  result.json gains "led_gains":
+//                      clip, gain [used][patches] as used last,
+//                      before_per_step / after_per_step [steps][patches] (the
+//                      patch sums of Q - 2 g C + g^2 S at the old and the new
+//                      gains), moments_ms.  Combines with --calibrate-leds (the
+//                      positions first) and --residual
 //
 // Device selection: OPENCV_OPENCL_DEVICE (set by use_gpu.sh / use_cpu.sh) is
 // read with OpenCV's "<platform>:<type>:<device>" grammar and the scripts'
@@ -59,6 +73,7 @@
 // MI355X ordinal; --device overrides it.
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -167,6 +182,7 @@ int main(int argc, char **argv) {
     std::string out_dir = ".", led_table, path_opt = "auto";
     int device = 0, device_opt = -1, gx = 0, gy = 0;
     bool want_residual = false;
+    bool want_gains = false;  // --calibrate-gains: one gain step between the iterations
     int cal_radius = -1;  // --calibrate-leds R: a window search of radius R between the iterations
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
@@ -175,6 +191,7 @@ int main(int argc, char **argv) {
         else if (a == "--led-table" && i + 1 < argc) led_table = argv[++i];
         else if (a == "--path" && i + 1 < argc) path_opt = argv[++i];
         else if (a == "--residual") want_residual = true;
+        else if (a == "--calibrate-gains") want_gains = true;
         else if (a == "--calibrate-leds" && i + 1 < argc) {
             cal_radius = atoi(argv[++i]);
             if (cal_radius < 1 || cal_radius > 8) {
@@ -394,11 +411,51 @@ int main(int argc, char **argv) {
         cal_moved.push_back(moved);
         return moved == 0 || fpm_set_crops(ctx, cal_x.data(), cal_y.data()) == 0;
     };
+    // --calibrate-gains: one estimate-and-apply step after every iteration but
+    // the last (fpm_amd.calibrate.estimate_gains' rule; stack index i == position i)
+    const double gain_lo = 0.25, gain_hi = 4.0;
+    std::vector<float> gain((size_t)used * B, 1.0f);
+    std::vector<std::vector<double>> gain_before, gain_after;  // [step][patch]
+    double gain_ms = 0;
+    auto calibrate_gains = [&]() {
+        const size_t n = (size_t)used * B;
+        std::vector<double> q(n), c(n), s(n);
+        double ms = 0;
+        if (fpm_moments(ctx, nullptr, 0, q.data(), c.data(), s.data(), &ms)) return false;
+        gain_ms += ms;
+        std::vector<float> next = gain;
+        std::vector<double> before(B, 0.0), after(B, 0.0);
+        for (int b = 0; b < B; ++b) {
+            double sw = 0, swg = 0;
+            for (int i = 0; i < used; ++i) {
+                const size_t k = (size_t)i * B + b;
+                if (!(s[k] > 0)) continue;
+                const double g = c[k] / s[k];
+                sw += s[k];
+                swg += s[k] * g * g;
+            }
+            const double scale = swg > 0 ? std::sqrt(sw / swg) : 0.0;
+            for (int i = 0; i < used; ++i) {
+                const size_t k = (size_t)i * B + b;
+                if (s[k] > 0 && swg > 0)
+                    next[k] = (float)std::min(gain_hi, std::max(gain_lo, c[k] / s[k] * scale));
+                const double g0 = gain[k], g1 = next[k];
+                before[b] += q[k] - 2 * g0 * c[k] + g0 * g0 * s[k];
+                after[b] += q[k] - 2 * g1 * c[k] + g1 * g1 * s[k];
+            }
+        }
+        gain_before.push_back(before);
+        gain_after.push_back(after);
+        if (fpm_set_gains(ctx, next.data())) return false;
+        gain.swap(next);
+        return true;
+    };
     auto t_all = std::chrono::steady_clock::now();
     for (int itr = 1; itr <= itr_count; ++itr) {
         auto t0 = std::chrono::steady_clock::now();
         if ((rc = fpm_run(ctx, 1)) || (want_residual && !residual()) ||
-            (cal_radius > 0 && itr < itr_count && !calibrate())) {
+            (cal_radius > 0 && itr < itr_count && !calibrate()) ||
+            (want_gains && itr < itr_count && !calibrate_gains())) {
             std::cerr << "fpm: " << fpm_last_error() << std::endl;
             return 1;
         }
@@ -483,6 +540,25 @@ int main(int argc, char **argv) {
                 fprintf(f, "], \"crop_y0\": [");
                 for (int i = 0; i < used; ++i) fprintf(f, "%s%d", i ? ", " : "", cal_y[i]);
                 fprintf(f, "], \"probe_ms\": %.6f},\n", cal_ms);
+            }
+            if (want_gains) {  // in processing order (stack index i == position i)
+                fprintf(f, "  \"led_gains\": {\"clip\": [%g, %g], \"gain\": [", gain_lo, gain_hi);
+                for (int i = 0; i < used; ++i) {
+                    fprintf(f, "%s[", i ? ", " : "");
+                    for (int b = 0; b < B; ++b) fprintf(f, "%s%.9g", b ? ", " : "", (double)gain[(size_t)i * B + b]);
+                    fprintf(f, "]");
+                }
+                const std::vector<std::vector<double>> *sums[2] = {&gain_before, &gain_after};
+                const char *names[2] = {"before_per_step", "after_per_step"};
+                for (int w = 0; w < 2; ++w) {
+                    fprintf(f, "], \"%s\": [", names[w]);
+                    for (size_t k = 0; k < sums[w]->size(); ++k) {
+                        fprintf(f, "%s[", k ? ", " : "");
+                        for (int b = 0; b < B; ++b) fprintf(f, "%s%.17g", b ? ", " : "", (*sums[w])[k][b]);
+                        fprintf(f, "]");
+                    }
+                }
+                fprintf(f, "], \"moments_ms\": %.6f},\n", gain_ms);
             }
             if (grid) {
                 fprintf(f, "  \"grid\": {\"gx\": %d, \"gy\": %d, \"patches\": %d, \"frame\": [%d, %d], "

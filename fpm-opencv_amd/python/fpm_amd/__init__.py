@@ -50,6 +50,7 @@ HIP_SYMBOLS = (
     "fpm_get_timing", "fpm_runFPM", "fpm_last_error", "fpm_version",
     "fpm_upload_frames", "fpm_download_stack", "fpm_get_info_sized", "fpm_abi_version",
     "fpm_get_clock", "fpm_residual", "fpm_residual_at", "fpm_set_crops", "fpm_get_crops",
+    "fpm_set_gains", "fpm_get_gains", "fpm_moments",
 )
 # test-only entry points (include/fpm_hip_debug.h)
 HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan",
@@ -166,6 +167,9 @@ def load_library(path: str = HIP_LIB):
                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "fpm_set_crops": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
         "fpm_get_crops": (C.c_int, [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "fpm_set_gains": (C.c_int, [vp, f32p]),
+        "fpm_get_gains": (C.c_int, [vp, f32p]),
+        "fpm_moments": (C.c_int, [vp, C.POINTER(fpm_probe), C.c_int] + [C.POINTER(C.c_double)] * 4),
         "fpm_runFPM": (C.c_int, [C.POINTER(fpm_problem), C.c_int, u16p, C.c_int,
                                  f32p, f32p, f32p, f32p]),
         "fpm_upload_frames": (C.c_int, [vp, C.POINTER(fpm_frames), vp, C.c_int, C.POINTER(C.c_int16)]),
@@ -323,7 +327,7 @@ class Solver:
 
     def residual(self):
         """Data-fidelity residual of the current state (fpm_residual; read-only,
-        blocking): err[i][b] = sum (|psi| - sqrt(I))^2 and ref[i][b] = sum I for
+        blocking): err[i][b] = sum (|psi| - g sqrt(I))^2 (g: gains()) and ref[i][b] = sum I for
         the LED at order[i] and patch b, float64 [n_order][n_patch], and the
         sweep's event time ms."""
         p = self.prob
@@ -334,11 +338,8 @@ class Solver:
         _check(_lib.fpm_residual(self._h, err.ctypes.data_as(dp), ref.ctypes.data_as(dp), C.byref(ms)))
         return dict(err=err, ref=ref, ms=ms.value)
 
-    def residual_at(self, pos, dx, dy):
-        """fpm_residual_at: the residual of the current state for the image of
-        order[pos[k]] with its window moved by (dx[k], dy[k]) from the crop
-        table's; equal-length integer arrays.  err / ref are float64
-        [n][n_patch], row k = entry k; read-only, blocking."""
+    @staticmethod
+    def _probes(pos, dx, dy):
         pos, dx, dy = _i32(pos).ravel(), _i32(dx).ravel(), _i32(dy).ravel()
         if not (len(pos) == len(dx) == len(dy)):
             raise ValueError("pos, dx and dy must have one length")
@@ -346,12 +347,61 @@ class Solver:
         probes = (fpm_probe * max(n, 1))()
         for k in range(n):
             probes[k] = fpm_probe(int(pos[k]), int(dx[k]), int(dy[k]))
+        return probes, n
+
+    def residual_at(self, pos, dx, dy):
+        """fpm_residual_at: the residual of the current state for the image of
+        order[pos[k]] with its window moved by (dx[k], dy[k]) from the crop
+        table's; equal-length integer arrays.  err / ref are float64
+        [n][n_patch], row k = entry k; read-only, blocking."""
+        probes, n = self._probes(pos, dx, dy)
         err = np.empty((n, self.prob.n_patch), np.float64)
         ref = np.empty_like(err)
         ms = C.c_double()
         dp = C.POINTER(C.c_double)
         _check(_lib.fpm_residual_at(self._h, probes, n, err.ctypes.data_as(dp), ref.ctypes.data_as(dp), C.byref(ms)))
         return dict(err=err, ref=ref, ms=ms.value)
+
+    def moments(self, pos=None, dx=None, dy=None):
+        """fpm_moments: the raw sums a gain is estimated from, of the current
+        state: model Q = sum |psi|^2, cross C = sum |psi| sqrt(I), ref S = sum I,
+        float64 [n][n_patch], and the sweep's event time ms.  Without arguments
+        the rows are the positions of order[] (as residual()); with pos / dx / dy
+        they are residual_at's entries.  The gain table does not enter:
+        E(g) = Q - 2 g C + g^2 S.  Read-only, blocking."""
+        if pos is None:
+            if dx is not None or dy is not None:
+                raise ValueError("dx / dy without pos")
+            probes, n = None, len(self.prob.order)
+        else:
+            probes, n = self._probes(pos, np.zeros_like(_i32(pos)) if dx is None else dx,
+                                     np.zeros_like(_i32(pos)) if dy is None else dy)
+        out = [np.empty((n, self.prob.n_patch), np.float64) for _ in range(3)]
+        ms = C.c_double()
+        dp = C.POINTER(C.c_double)
+        _check(_lib.fpm_moments(self._h, probes, n, *(a.ctypes.data_as(dp) for a in out), C.byref(ms)))
+        return dict(model=out[0], cross=out[1], ref=out[2], ms=ms.value)
+
+    def set_gains(self, g):
+        """fpm_set_gains: the per-image amplitude factor, float32
+        [n_stack][n_patch] ([n_stack] if n_patch == 1); None = all ones.  Every
+        value finite and > 0.  The state is kept."""
+        if g is None:
+            _check(_lib.fpm_set_gains(self._h, None))
+            return
+        want = (len(self.prob.x0), self.prob.n_patch)
+        a = np.ascontiguousarray(g, dtype=np.float32)
+        if a.ndim == 1 and want[1] == 1:
+            a = a[:, None]
+        if a.shape != want:
+            raise ValueError(f"gain shape {a.shape} != {want}")
+        _check(_lib.fpm_set_gains(self._h, _f32p(a)))
+
+    def gains(self) -> np.ndarray:
+        """float32 [n_stack][n_patch]: the gain table in use (fpm_get_gains)."""
+        g = np.empty((len(self.prob.x0), self.prob.n_patch), np.float32)
+        _check(_lib.fpm_get_gains(self._h, _f32p(g)))
+        return g
 
     def set_crops(self, x0, y0):
         """fpm_set_crops: replace the crop table [n_stack] of the live context;

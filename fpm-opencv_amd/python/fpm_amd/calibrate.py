@@ -1,4 +1,7 @@
-"""LED position calibration: one window-search step on a live Solver.
+"""LED calibration on a live Solver: positions (calibrate_positions) and
+brightness (calibrate_gains, at the end of this file).
+
+LED position calibration: one window-search step.
 
 A wrong illumination angle puts an LED's sub-aperture window a pixel or a few
 away from where the data says it is, and that LED's row of the residual
@@ -100,3 +103,74 @@ def calibrate_positions(solver, radius: int = 1) -> dict:
     rows = np.arange(len(order))
     return dict(offsets=offsets, shift=shift.astype(np.int32), table=table, before=sums[:, 0].copy(),
                 after=sums[rows, pick], moved=moved, ms=d["ms"])
+
+
+# ---- LED brightness ---------------------------------------------------------------
+# A wrong LED brightness (the LEDs of a dome differ, fluctuate between exposures
+# and fall off with angle; dark-field frames are divided by a nominal exposure
+# multiplier) scales an image by h^2, and that LED's row of E / S stands out
+# just as a misplaced one does.  The cure is a per-image amplitude factor g
+# (Solver.set_gains): the solver then uses g sqrt(I) wherever it used sqrt(I).
+# With Q = sum |psi|^2, C = sum |psi| sqrt(I) and S = sum I of the current
+# state (Solver.moments, one sweep on the GPU), E(g) = Q - 2 g C + g^2 S, so
+# the best factor for an image is C / S.
+
+
+def gain_error(g, Q, C, S):
+    """E(g) = Q - 2 g C + g^2 S, elementwise."""
+    g = np.asarray(g, np.float64)
+    return Q - 2.0 * g * C + g * g * S
+
+
+def estimate_gains(order, old, Q, C, S, clip=(0.25, 4.0)) -> np.ndarray:
+    """The rule of calibrate_gains on given moments: `old` float [n_stack][B],
+    Q / C / S float64 [n_order][B] (row i = order[i]).  Returns the new table.
+
+    g^ = C / S for every (LED, patch) that is used and has S > 0; the others
+    keep their gain.  A stack index that occurs at several positions of
+    order[] takes its first position's value.  Gain and object share a scale
+    (g -> s g, O -> s O changes nothing), so each patch's estimates are then
+    multiplied by one factor that makes the S-weighted mean of g^2 over them
+    1, and clipped to [lo, hi]."""
+    lo, hi = float(clip[0]), float(clip[1])
+    if not (0.0 < lo <= hi and np.isfinite(hi)):
+        raise ValueError(f"clip={clip}: want 0 < lo <= hi < inf")
+    new = np.array(old, np.float64)
+    C, S = np.asarray(C, np.float64), np.asarray(S, np.float64)
+    est = np.zeros(new.shape, bool)
+    w = np.zeros(new.shape)
+    seen = set()
+    for i, led in enumerate(int(v) for v in order):
+        if led in seen:
+            continue
+        seen.add(led)
+        ok = S[i] > 0
+        new[led, ok] = C[i, ok] / S[i, ok]
+        est[led] = ok
+        w[led, ok] = S[i, ok]
+    for b in range(new.shape[1]):
+        m = est[:, b]
+        den = float(np.sum(w[m, b] * new[m, b] ** 2))
+        if den > 0:
+            new[m, b] = np.clip(new[m, b] * np.sqrt(np.sum(w[m, b]) / den), lo, hi)
+        else:  # nothing to estimate from (the model is dark everywhere): leave the patch alone
+            new[m, b] = np.asarray(old, np.float64)[m, b]
+    return new.astype(np.float32)
+
+
+def calibrate_gains(solver, clip=(0.25, 4.0)) -> dict:
+    """One estimate-and-apply step on an initialised Solver (estimate_gains on
+    Solver.moments(), installed with Solver.set_gains).
+
+    Returns dict(old, new float32 [n_stack][n_patch], model / cross / ref
+    float64 [n_order][n_patch], before / after [n_order][n_patch] =
+    Q - 2 g C + g^2 S at the old and new gains of each position's LED, ms =
+    the moments sweep's event time)."""
+    order = np.asarray(solver.prob.order, np.int64)
+    old = solver.gains()
+    m = solver.moments()
+    Q, Cx, S = m["model"], m["cross"], m["ref"]
+    new = estimate_gains(order, old, Q, Cx, S, clip)
+    solver.set_gains(new)
+    return dict(old=old, new=new, model=Q, cross=Cx, ref=S, before=gain_error(old[order], Q, Cx, S),
+                after=gain_error(new[order], Q, Cx, S), ms=m["ms"])

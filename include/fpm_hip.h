@@ -37,9 +37,11 @@ extern "C" {
  * stream.  (6): fpm_residual added.  fpm_abi_version() reports the library's
  * revision.  Entry points appended since then change nothing a revision-6
  * caller sees, so the revision stands and each addition has a feature macro:
- * FPM_HAS_LED_CALIBRATION = fpm_residual_at, fpm_set_crops, fpm_get_crops. */
+ * FPM_HAS_LED_CALIBRATION = fpm_residual_at, fpm_set_crops, fpm_get_crops;
+ * FPM_HAS_LED_GAINS = fpm_set_gains, fpm_get_gains, fpm_moments. */
 #define FPM_ABI_VERSION   6
 #define FPM_HAS_LED_CALIBRATION 1
+#define FPM_HAS_LED_GAINS 1
 
 #define FPM_OK            0
 #define FPM_ERR_INVAL   (-22)   /* bad argument / unsupported geometry      */
@@ -202,8 +204,9 @@ int  fpm_run(fpm_ctx *ctx, int iters);
 
 /* Data-fidelity residual of the current state (read-only: spectrum, pupil,
  * maxima, objCrop and the stack are left bit for bit as they were).
- *   err [n_order][n_patch]  E = sum_yx (|psi| - sqrt(I))^2, psi = ifft2(window * P)
- *                           scaled 1/Np^2 like the reference's ifft2; no eps
+ *   err [n_order][n_patch]  E = sum_yx (|psi| - g sqrt(I))^2, psi = ifft2(window * P)
+ *                           scaled 1/Np^2 like the reference's ifft2; no eps;
+ *                           g the image's gain (fpm_set_gains; 1 by default)
  *   ref [n_order][n_patch]  S = sum_yx I  (exact)
  * Row i is order[i]'s LED.  Either pointer may be NULL, not both.
  * elapsed_ms (may be NULL): event-to-event time of the sweep on the run stream.
@@ -251,6 +254,40 @@ int  fpm_residual_at(fpm_ctx *ctx, const fpm_probe *probes, int n, double *err, 
  * table in use. */
 int  fpm_set_crops(fpm_ctx *ctx, const int32_t *crop_x0, const int32_t *crop_y0);
 int  fpm_get_crops(const fpm_ctx *ctx, int32_t *crop_x0, int32_t *crop_y0);
+
+/* LED gains: a per-image amplitude factor g [n_stack][n_patch] (float32,
+ * LED-major like the stack, all ones by default) for LEDs whose brightness or
+ * exposure differs from the nominal one.  Every consumer of a measured
+ * amplitude uses g sqrt(I) in place of sqrt(I): fpm_init's initial spectrum,
+ * the amplitude replacement of every LED step (psi' = g sqrt(I) psi / |psi + eps|,
+ * eps untouched) and E of fpm_residual / fpm_residual_at; S stays the raw sum.
+ * A gain of 1.0f is bit for bit no gain.
+ * fpm_set_gains: every value finite and > 0, and under FPM_FLAG_SPEC_FP16
+ * 256 g < 65504 (the headroom of the fp16 spectrum); otherwise FPM_ERR_INVAL
+ * naming the first bad index, the context unchanged.  NULL = all ones.  Legal
+ * before and after fpm_init and between fpm_run calls; blocking (waits for
+ * the run stream); FPM_ERR_INVAL on a capturing stream.  Spectrum, pupil,
+ * maxima and stack are untouched.  fpm_get_gains copies the table in use. */
+int  fpm_set_gains(fpm_ctx *ctx, const float *gain);
+int  fpm_get_gains(const fpm_ctx *ctx, float *gain);
+
+/* The sums a gain is estimated from, of the current state:
+ *   model [n][n_patch]  Q = sum_yx |psi|^2
+ *   cross [n][n_patch]  C = sum_yx |psi| sqrt(I)
+ *   ref   [n][n_patch]  S = sum_yx I  (exact)
+ * with psi as fpm_residual's.  Raw: the gain table does not enter, so for any g
+ *   E(g) = Q - 2 g C + g^2 S,   argmin_g E = C / S,   min_g E = Q - C^2 / S.
+ * probes == NULL: the context's own list (n is ignored; row i is order[i]'s
+ * LED, as fpm_residual's); otherwise fpm_residual_at's entries, validation and
+ * row order, so the best window under an unknown brightness is the entry that
+ * minimises Q - C^2 / S.  Any output pointer may be NULL, not all of them.
+ * The contract of fpm_residual_at: read-only, blocking, deterministic (an
+ * entry's bits depend on the state and that entry alone); FPM_ERR_STATE before
+ * fpm_init; FPM_ERR_INVAL on a capturing stream before anything is enqueued.
+ * It runs the residual sweep's kernels and scratch plus two buffers of sums of
+ * its own, allocated by its first call. */
+int  fpm_moments(fpm_ctx *ctx, const fpm_probe *probes, int n, double *model, double *cross,
+                 double *ref, double *elapsed_ms);
 
 /* Wait for all work on the context stream. */
 int  fpm_synchronize(fpm_ctx *ctx);

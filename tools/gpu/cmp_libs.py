@@ -6,7 +6,13 @@ device bytes allocated) and the residual sweep's err / ref (fpm_residual after
 the run: read-only, so it disturbs nothing before it; its scratch is part of
 device_bytes, read after it) are compared exactly.
 
-usage: python tools/gpu/cmp_libs.py <lib_a.so> <lib_b.so>
+usage: python tools/gpu/cmp_libs.py [--allow-bytes] [--python-a DIR] <lib_a.so> <lib_b.so>
+  --python-a DIR  lib_a is an older commit's build whose exports this tree's
+                  Python mirror no longer matches: DIR is that commit's
+                  fpm-opencv_amd/python
+  --allow-bytes   a change that adds a device buffer (the LED gain table): the
+                  device_bytes may differ (the difference is printed), every
+                  other figure and every output bit may not
 """
 import os
 import subprocess
@@ -50,7 +56,8 @@ CASES = [  # (name, environment, geometry)
 
 CHILD = r"""
 import sys, numpy as np
-sys.path.insert(0, 'fpm-opencv_amd/python'); sys.path.insert(0, '.')
+import os
+sys.path.insert(0, os.environ.get('CMP_PYTHON') or 'fpm-opencv_amd/python'); sys.path.insert(0, '.')
 import fpm_amd
 from tools.synth import grid_geometry, make_stack
 Np, L, r, nside, step = (int(v) for v in sys.argv[2:7])
@@ -76,27 +83,40 @@ np.savez(sys.argv[1], info=info, err=np.asarray(res["err"]), ref=np.asarray(res[
 """
 
 
-def run(lib, env, geo, path):
+def run(lib, env, geo, path, python=""):
     e = dict(os.environ, FPM_HIP_LIB=os.path.abspath(lib), **env)
+    if python:
+        e["CMP_PYTHON"] = os.path.abspath(python)
     subprocess.run([sys.executable, "-c", CHILD, path, *map(str, geo)], check=True, env=e, timeout=300)
 
 
 def main():
-    a, b = sys.argv[1], sys.argv[2]
+    argv = [v for v in sys.argv[1:] if v != "--allow-bytes"]
+    allow_bytes = len(argv) != len(sys.argv) - 1
+    python_a = ""
+    if "--python-a" in argv:
+        i = argv.index("--python-a")
+        python_a = argv[i + 1]
+        del argv[i:i + 2]
+    a, b = argv[0], argv[1]
     ok = True
     with tempfile.TemporaryDirectory() as d:
         for name, env, geo in CASES:
             pa, pb = os.path.join(d, f"{name}_a.npz"), os.path.join(d, f"{name}_b.npz")
-            run(a, env, geo, pa)
+            run(a, env, geo, pa, python_a)
             run(b, env, geo, pb)
-            za, zb = np.load(pa), np.load(pb)
-            same = all(np.array_equal(za[k], zb[k]) for k in za.files)
+            za, zb = dict(np.load(pa)), dict(np.load(pb))
+            extra = ""
+            if allow_bytes and za["info"][3] != zb["info"][3]:
+                extra = f" (device_bytes {int(za['info'][3])} -> {int(zb['info'][3])})"
+                zb["info"][3] = za["info"][3]
+            same = all(np.array_equal(za[k], zb[k]) for k in za)
             ok = ok and same
             if same:
-                print(f"{name}: bit-identical")
+                print(f"{name}: bit-identical{extra}")
             else:  # which outputs moved, by how much (relative L2)
                 rel = {k: float(np.linalg.norm(za[k] - zb[k]) / max(np.linalg.norm(za[k]), 1e-30))
-                       for k in za.files if not np.array_equal(za[k], zb[k])}
+                       for k in za if not np.array_equal(za[k], zb[k])}
                 if "info" in rel:
                     print(f"{name}: info {za['info'].tolist()} != {zb['info'].tolist()}")
                 print(f"{name}: DIFFERENT " + " ".join(f"{k} rel {v:.2e}" for k, v in rel.items()))
