@@ -1,7 +1,7 @@
 // api.cpp -- the small entry points of the extern "C" boundary of
 // libfpm_hip.so (include/fpm_hip.h): the last error, the versions, what a
-// context reports about itself (info, timing, clock), the debug setter and the
-// one-shot fpm_runFPM.  The boundary mirrors runFPM(FPM_Dataset*)
+// context reports about itself (info, timing, clock), the context-based debug
+// entries (include/fpm_hip_debug.h) and the one-shot fpm_runFPM.  The boundary mirrors runFPM(FPM_Dataset*)
 // (fpmMain.cpp:274-498); the rest of it is in create.cpp, transfer.cpp and
 // run.cpp (ctx.hpp).
 #include <algorithm>
@@ -129,6 +129,46 @@ int fpm_debug_get_maxima(const fpm_ctx *c, int *dims, float *tmax, unsigned char
                 if ((bits[b * nw + (k >> 5)] >> (k & 31)) & 1u)
                     dirty[b * nt + (size_t)(band.bty0 + k / band.nbx) * st.ntx + band.btx0 + k % band.nbx] = 1;
     }
+    return FPM_OK;
+}
+
+int fpm_debug_objcrop(fpm_ctx *c, const float *spec, const int band[4], float *objcrop) {
+    if (!c || !spec || !band || !objcrop) return set_err(FPM_ERR_INVAL, "null argument");
+    const int L = c->st.L;
+    if (band[0] < 0 || band[0] > band[1] || band[1] >= L || band[2] < 0 || band[2] > band[3] || band[3] >= L)
+        return set_err(FPM_ERR_INVAL, "fpm_debug_objcrop: band rows [%d, %d] columns [%d, %d] outside 0 <= lo <= hi < %d",
+                       band[0], band[1], band[2], band[3], L);
+    HIP_TRY(hipSetDevice(c->device));
+    int rc = refuse_capture(c, "fpm_debug_objcrop");
+    if (rc) return rc;
+    // the spectrum is overwritten: whatever the context held is gone
+    c->initialized = false;
+    c->objcrop_valid = false;
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // the context's state with the caller's band; the planned one stays in c->st
+    DevState st = c->st;
+    st.sy0 = band[0];
+    st.sy1 = band[1];
+    st.sx0 = band[2];
+    st.sx1 = band[3];
+    const size_t ll = (size_t)L * L, n = (size_t)st.B * ll;
+    if (st.spec16) {  // as spec_st stores it (fpm_state.hpp)
+        const float2 *src = (const float2 *)spec;
+        std::vector<__half2> h16(ll);
+        for (int b = 0; b < st.B; ++b) {
+            for (size_t i = 0; i < ll; ++i) {
+                const float2 v = src[b * ll + i];
+                h16[i] = __float22half2_rn(make_float2(v.x * st.hscale, v.y * st.hscale));
+            }
+            HIP_TRY(hipMemcpy(st.spec16 + b * ll, h16.data(), ll * sizeof(__half2), hipMemcpyHostToDevice));
+        }
+    } else {
+        HIP_TRY(hipMemcpy(st.spec, spec, n * sizeof(float2), hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipMemsetAsync(c->objcrop, 0xFF, n * sizeof(float2), c->stream));
+    HIP_TRY(launch_objcrop(st, c->objcrop, c->pl_L, c->tw_L, c->sw, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(objcrop, c->objcrop, n * sizeof(float2), hipMemcpyDeviceToHost));
     return FPM_OK;
 }
 

@@ -54,7 +54,7 @@ HIP_SYMBOLS = (
 )
 # test-only entry points (include/fpm_hip_debug.h)
 HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan",
-                     "fpm_debug_get_maxima", "fpm_debug_plan_ladder", "fpm_debug_get_ladder")
+                     "fpm_debug_get_maxima", "fpm_debug_plan_ladder", "fpm_debug_get_ladder", "fpm_debug_objcrop")
 # fpm_ladder_kernel.generation
 LADDER_ONE_SEQ, LADDER_TILED, LADDER_WAVE = 0, 1, 2
 # fpm_debug_get_plan: general_kind / residual_kind values
@@ -160,6 +160,7 @@ def load_library(path: str = HIP_LIB):
         "fpm_debug_get_maxima": (C.c_int, [vp, C.POINTER(C.c_int), f32p, C.POINTER(C.c_uint8), f32p, f32p]),
         "fpm_debug_plan_ladder": (C.c_int, [C.c_int] * 6 + [C.POINTER(fpm_ladder)]),
         "fpm_debug_get_ladder": (C.c_int, [vp, C.c_int, C.POINTER(fpm_ladder)]),
+        "fpm_debug_objcrop": (C.c_int, [vp, f32p, C.POINTER(C.c_int), f32p]),
         "fpm_get_timing": (C.c_int, [vp, C.POINTER(fpm_timing)]),
         "fpm_get_clock": (C.c_int, [vp, C.POINTER(fpm_clock)]),
         "fpm_residual": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -479,6 +480,23 @@ class Solver:
         l = fpm_ladder()
         _check(_lib.fpm_debug_get_ladder(self._h, int(residual), C.byref(l)))
         return l.as_dict()
+
+    def debug_objcrop(self, spec, band) -> np.ndarray:
+        """Test-only (include/fpm_hip_debug.h): objCrop of the CENTRED spectrum
+        `spec`, complex64 [n_patch][L][L], with the live band (sy0, sy1, sx0, sx1)
+        inclusive, through the context's own objCrop launch; complex64
+        [n_patch][L][L].  The context's state is gone afterwards: init() again
+        before run() or download()."""
+        p = self.prob
+        a = np.ascontiguousarray(spec, dtype=np.complex64)
+        want = (p.n_patch, p.L, p.L)
+        if a.shape != want:
+            raise ValueError(f"spectrum shape {a.shape} != {want}")
+        if len(band) != 4:
+            raise ValueError("band is (sy0, sy1, sx0, sx1)")
+        out = np.empty(want, np.complex64)
+        _check(_lib.fpm_debug_objcrop(self._h, _f32p(a), (C.c_int * 4)(*(int(v) for v in band)), _f32p(out)))
+        return out
 
     def timing(self) -> fpm_timing:
         t = fpm_timing()

@@ -92,6 +92,23 @@ int fpm_debug_plan_ladder(int np, int nb, int B, int step, int no_wave_cols, int
  * they differ. */
 int fpm_debug_get_ladder(const fpm_ctx *ctx, int residual, fpm_ladder *out);
 
+/* objCrop of a given spectrum and live band, through the product's own
+ * launch_objcrop (objcrop.hip, fft_batch.hip): no kernel and no dispatch of
+ * its own.  Legal on any created context; needs neither a stack nor fpm_init.
+ *   spec    [B][L][L][2]  the CENTRED spectrum, copied verbatim into the
+ *                         context's spectrum buffer (FPM_FLAG_SPEC_FP16: stored
+ *                         as half(v * hscale), as every kernel stores it)
+ *   band    sy0, sy1, sx0, sx1, inclusive: the live band the kernels are told
+ *           (0 <= lo <= hi < L); what spec holds outside it must not matter
+ *   objcrop [B][L][L][2]  the result.  The context's objCrop buffer is filled
+ *                         with 0xFF bytes (NaN) before the launch, so an element
+ *                         no pass writes, or an intermediate row read although
+ *                         no pass wrote it, shows in the result.
+ * Blocking.  FPM_ERR_INVAL on a null argument, a band outside the spectrum and
+ * a capturing stream.  The context's planned band is kept, its state is not:
+ * fpm_run and fpm_download return FPM_ERR_STATE until fpm_init is called. */
+int fpm_debug_objcrop(fpm_ctx *ctx, const float *spec, const int band[4], float *objcrop);
+
 #ifdef __cplusplus
 }
 #endif
