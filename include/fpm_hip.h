@@ -65,7 +65,16 @@ extern "C" {
  *   bg     = (mean(bk1 window) + mean(bk2 window)) / 2 of the UNDIVIDED
  *            frame, clamped to bg_threshold, rounded to int16   (:131-140)
  *   Image  = saturate(Image - bg)                               (:143-144)
- * Background windows are Np x Np and shared by all patches of a frame.
+ * Background windows are Np x Np and shared by all patches of a frame; they
+ * may coincide with each other and with a patch.  The divide rounds half to
+ * even (5 / 2 -> 2, 7 / 2 -> 4) and saturates at 65535 (a multiplier below 1);
+ * bg rounds half away from zero (999.5 -> 1000, -7.5 -> -8); the subtraction
+ * saturates at 0 and, with a negative bg_threshold, at 65535.  darkfield[i] is
+ * read as a flag: any nonzero value divides.  The window sums are exact at
+ * every Np (64-bit).  All of this is pinned bit for bit against the oracle's
+ * restatement, on every stack layout a context can have
+ * (tests/preprocess_cases.py).  Out of contract: a background above 32767,
+ * where the reference's (int16_t)round(bg) is undefined.
  */
 typedef struct fpm_frames {
     int32_t height, width;        /* full frame size                              */

@@ -205,6 +205,8 @@ def preprocess_frame(frame, np_: int, crop, bk1, bk2, bg_threshold: float, dark_
     bg = (mean(bk2) + mean(bk1)) / 2
     if bg > bg_threshold:
         bg = float(bg_threshold)
-    bg_val = int(np.floor(bg + 0.5))                       # std::round, bg >= 0
+    # round() of <cmath> at :140: half away from zero (a negative bgThresh of
+    # k + 0.5 rounds down, which floor(bg + 0.5) alone would not)
+    bg_val = int(np.copysign(np.floor(abs(bg) + 0.5), bg))
     bg_val = (bg_val + 32768) % 65536 - 32768               # (int16_t) conversion
     return np.clip(img - bg_val, 0, 65535).astype(np.uint16), bg_val

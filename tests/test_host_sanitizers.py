@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from dataset_fixture import make_dataset
+from dataset_fixture import make_case_dataset, make_dataset
 from fpm_amd import host
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -60,6 +60,11 @@ def test_json_geometry_loader_under_asan_ubsan(driver, tmp_path):
         p = tmp_path / f"v{i}.json"
         p.write_bytes(text.encode("latin-1", "replace"))
         files.append(str(p))
+    # the loader's rounding ties, clamps and coinciding windows (tests/preprocess_cases.py)
+    import preprocess_cases as pc
+    for name in ("dark_tie_even", "dark_tie_odd", "bg_tie", "bg_negative_threshold", "bg_max_int16",
+                 "windows_overlap", "frame_is_patch"):
+        files.append(make_case_dataset(str(tmp_path / name), pc.CASE[name], 32)["json"])
     _run(driver, "json", files)
 
 
