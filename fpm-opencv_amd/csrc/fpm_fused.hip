@@ -6,7 +6,7 @@
 //
 // Per LED step, per workgroup (R = naRadius, box = 2R+1 rows, 16-lane groups):
 //   gather  O = spec[yc+ky][xc+kx] on the support into registers   (:358-362)
-//   for each half h of the columns (x in [128h, 128h+128)):
+//   for each half h of the columns (x mod 16 in [8h, 8h+8)):
 //     A  row IDFTs of the box rows of O*P (:364-365), the half's 128
 //        outputs -> LDS half-T (64 FFT rows + <= 8 "tail" rows by direct sums)
 //     B  per column x: column IDFT (only box rows are non-zero), 1/Np^2,
@@ -32,6 +32,20 @@
 // forward ones are pruned to those six registers.  Box rows beyond the 64
 // FFT rows ("tail rows", the outermost rows of the disk with a handful of
 // pixels) are transformed by direct DFT sums spread over all threads.
+//
+// The row passes A and C transform the two FFT rows of a group together.  T
+// does not fit in LDS whole, so a row transform can only keep (A) or take (C)
+// half of its 256 columns at a time.  The halves are cut on the LOW digit of
+// the column, x = x1 + 16 x2 with x1 in [8h, 8h+8): the pruned side of the
+// four-step transform (six registers, lane = kx mod 16) then needs only 8 of
+// its 16 stage-1 values per row, the two rows' 8 + 8 fill one exchange tile,
+// and the dense 16-point DFT on the other side runs once for both rows --
+// lanes 0-7 hold (row 0, x1 = 8h + lane), lanes 8-15 (row 1, x1 = 8h + lane
+// - 8), each with the 16 x2 of its column digit (fused256.hpp "row pairs").
+// A half-T row holds its 128 columns as xl = (x1 - 8h) + 8 x2, and pass B,
+// the measurement address and the tail sums turn xl back into x (xcol).
+// (Halves cut on the high digit, x in [128h, 128h+128), ran a whole transform
+// per row and half and threw half of it away: DESIGN.md 4.1.)
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -52,8 +66,11 @@ namespace fpm {
 // Column parts: T (the row IDFTs of the box rows) is held in LDS one column
 // part at a time -- two halves of 128 columns walked in turn by the
 // one-workgroup kernel (KS = 1), or the one part a split-mode workgroup owns
-// (KS = 2: a half, KS = 4: a quarter of 64 columns).  Row pitch part + 1
-// complex, so the 16 lanes of a column read hit 16 different bank pairs.
+// (KS = 2: a half, KS = 4: a quarter).  A half is the columns with x mod 16 in
+// [8h, 8h+8) (row pairs, see the file header); a quarter is 64 contiguous
+// columns, one transform per row (a quarter cut on the low digit would need
+// four rows per group).  Row pitch part + 1 complex, so the 16 lanes of a
+// column read hit 16 different bank pairs.
 constexpr int n_parts(int ks) { return ks == 1 ? 2 : ks; }
 constexpr int part_cols(int ks) { return fz::NP / n_parts(ks); }
 
@@ -69,6 +86,8 @@ struct FzCfg {
     static constexpr int RPG = fz::NROWS / NG;    // FFT rows per group
     static constexpr int NW = NT / 64;            // waves
     static constexpr int XT = XTILE;              // exchange tile per group (complex)
+    // FFT row (T row, ky - ky_lo) of row j of group g
+    static __device__ __forceinline__ int row(int g, int j) { return g + NG * j; }
 };
 
 // KS workgroups per patch: 1 (both column halves in turn), or split mode with
@@ -83,6 +102,10 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
     static_assert(KS == 1 || KS == 2 || KS == 4, "one workgroup per patch, or split mode with 2 / 4");
     static_assert(6 * RPG * 16 <= C::XT, "pupil numerators are parked in the group's exchange tile");
     constexpr int NPARTS = n_parts(KS), TH = part_cols(KS), TLD = TH + 1;
+    // two halves: cut on the low column digit, one four-step transform per
+    // pass serves both rows of a group (lanes 0-7 row 0, lanes 8-15 row 1)
+    constexpr bool PAIR = NPARTS == 2;
+    static_assert(!PAIR || RPG == 2, "a row pair per group");
     extern __shared__ __attribute__((aligned(16))) float2 sm[];
     const int nrows = NROWS + a.n_tail_rows;
     float2 *scr_all = sm;                           // NG * XT: per-group exchange tiles
@@ -161,8 +184,8 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
     unsigned inmask[RPG];
 #pragma unroll
     for (int j = 0; j < RPG; ++j) {
-        kyr[j] = a.ky_lo + g + NG * j;
-        ron[j] = g + NG * j < a.n_fft_rows;
+        kyr[j] = a.ky_lo + C::row(g, j);
+        ron[j] = C::row(g, j) < a.n_fft_rows;
         inmask[j] = 0;
 #pragma unroll
         for (int s = 0; s < 6; ++s) {
@@ -187,6 +210,11 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
         roff[s] = sg >= 0 ? sg * TLD : zoff;
     }
     for (int i = tid; i < TLD; i += NT) th[zoff + i] = make_float2(0.f, 0.f);
+    // row pairs: half-T offset of this lane's row (t >> 3) of the group in
+    // passes A and C; a row that is off reads the zero row and writes the dummy
+    const int pj = t >> 3;
+    const bool pon = pj ? ron[RPG - 1] : ron[0];
+    const int prow = (pon ? C::row(g, pj) * TLD : zoff) + (t & 7);
     const bool towner = tid < a.n_tail_px;
     const int2 tp = towner ? tpx[tid] : make_int2(0, 0);
     float2 Pt = towner ? pup[(tp.x + R) * NB + tp.y + R] : make_float2(0.f, 0.f);
@@ -329,43 +357,48 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
             // loaded at the top of each pass-B round (one round ahead measured
             // 5 % slower: 16 VGPRs the scheduler needs)
             // pass B works on 32 column blocks per half: block r8 gives group gg
-            // of a wave column (r8 & 15) + 16 gg + 64 (r8 >> 4)
+            // of a wave the half-T slot xl = (r8 & 15) + 16 gg + 64 (r8 >> 4)
             constexpr int NBLK = TH / 4;
             auto colx = [&](int r8) { return (r8 & 15) + 16 * gg + 64 * (r8 >> 4); };
+            // the image column of slot xl of this part's half-T row: two
+            // halves hold x1 = x mod 16 in [8h, 8h+8) as xl = (x1 - 8h) + 8 x2;
+            // four parts hold 64 contiguous columns
+            auto xcol = [&](int xl) { return PAIR ? 8 * h + (xl & 7) + 16 * (xl >> 3) : xl + TH * h; };
             // the lane's 16 uint16 pixels of column x: 32 contiguous bytes
             auto ldI = [&](int xl, uint4 (&n)[2]) {
-                const uint4 *ip = (const uint4 *)(Ib + ((xl + TH * h) * 16 + t) * 16);
+                const uint4 *ip = (const uint4 *)(Ib + (xcol(xl) * 16 + t) * 16);
 #pragma unroll
                 for (int i = 0; i < 2; ++i) n[i] = ld_stream(ip + i);
             };
-            // ---- A: row IDFTs of the box rows, columns [128h, 128h+128) kept
+            // ---- A: row IDFTs of the box rows, the columns of part h kept
             float2 X[RPG][6];
 #pragma unroll
             for (int j = 0; j < RPG; ++j)
 #pragma unroll
                 for (int s = 0; s < 6; ++s) X[j][s] = pout(pmul(pin(Opre[j][s]), pin(P[j][s])));   // :364
+            if constexpr (PAIR) {
+                // both rows in one transform; lane t keeps the 16 x2 of
+                // (row t >> 3, x1 = 8h + (t & 7)): row[8 x2]
+                if (ron[0]) {
+                    idft256_pair_in6(X, v, r, scr, wt, t, xrd, h);
+                    float2 *row = th + prow + (pon ? 0 : TLD);
 #pragma unroll
-            for (int j = 0; j < RPG; ++j) {
-                if (!ron[j]) continue;
+                    for (int m = 0; m < 16; ++m) row[8 * m] = r[m];
+                }
+            } else {
 #pragma unroll
-                for (int k = 0; k < 16; ++k) v[k] = make_float2(0.f, 0.f);
+                for (int j = 0; j < RPG; ++j) {
+                    if (!ron[j]) continue;
 #pragma unroll
-                for (int s = 0; s < 6; ++s) v[SK[s]] = X[j][s];
-                idft256_in6(v, r, scr, wt, t, xrd);
-                // keep the column part h: row[16 m'] = r[h MPP + m'] (one branch
-                // per part keeps every register index static; a shared helper
-                // made the compiler select between addresses of r and put r
-                // in scratch)
-                float2 *row = th + (g + NG * j) * TLD + t;
-                if constexpr (NPARTS == 2) {
-                    if (h == 0) {
+                    for (int k = 0; k < 16; ++k) v[k] = make_float2(0.f, 0.f);
 #pragma unroll
-                        for (int m = 0; m < 8; ++m) row[16 * m] = r[m];
-                    } else {
-#pragma unroll
-                        for (int m = 0; m < 8; ++m) row[16 * m] = r[8 + m];
-                    }
-                } else {
+                    for (int s = 0; s < 6; ++s) v[SK[s]] = X[j][s];
+                    idft256_in6(v, r, scr, wt, t, xrd);
+                    // keep the column part h: row[16 m'] = r[h MPP + m'] (one branch
+                    // per part keeps every register index static; a shared helper
+                    // made the compiler select between addresses of r and put r
+                    // in scratch)
+                    float2 *row = th + C::row(g, j) * TLD + t;
                     if (h == 0) {
 #pragma unroll
                         for (int m = 0; m < 4; ++m) row[16 * m] = r[m];
@@ -388,7 +421,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
                 // q is wave-uniform (TH = 1 or 2 waves): the row's pixel range comes
                 // from scalar loads; kx runs over a contiguous range, so the
                 // twiddle index advances by x per term
-                const int q = idx / TH, xl = idx - q * TH, x = xl + TH * h;
+                const int q = idx / TH, xl = idx - q * TH, x = xcol(xl);
                 const int p0 = a.tail_row_p0[q], np_ = a.tail_row_np[q];
                 // twiddle W^{-x kx} by recurrence from two table values: a
                 // per-term table read with lane-dependent x conflicts on LDS banks
@@ -412,7 +445,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
             __syncthreads();  // half-T complete
             FPM_STAMP(1)
 
-            // ---- B: columns x in [128h, 128h+128): IDFT, amplitude replacement, DFT (:365-394)
+            // ---- B: the columns of part h: IDFT, amplitude replacement, DFT (:365-394)
             // Column blocks are claimed dynamically (NT 512): wave w starts with
             // block w and takes the next unclaimed block from an LDS counter.  At
             // two waves per SIMD the VALU arbiter favours the older wave of each
@@ -474,28 +507,50 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
             for (int j = 0; j < RPG; ++j)
 #pragma unroll
                 for (int s = 0; s < 6; ++s) Opre[j][s] = ldO(srow, j, s);
+            if constexpr (PAIR) {
+                if (ron[0]) {
+                    // the four-step twiddles of the lane's column digit x1 =
+                    // 8h + (t & 7); pass B's set is reloaded at the top of a half
+                    wt.load(tw2, 8 * h + (t & 7));
 #pragma unroll
-            for (int j = 0; j < RPG; ++j) {
-                if (!ron[j]) {
+                    for (int m = 0; m < 16; ++m) v[m] = th[prow + 8 * m];
+                    float2 o[RPG][6];
+                    dft256_pair_out6(v, o, scr, wt, t, xrd, h);
 #pragma unroll
-                    for (int s = 0; s < 6; ++s) F[j][s] = make_float2(0.f, 0.f);
-                    continue;
+                    for (int j = 0; j < RPG; ++j)
+#pragma unroll
+                        for (int s = 0; s < 6; ++s) F[j][s] = h == hb ? o[j][s] : cadd(F[j][s], o[j][s]);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < RPG; ++j)
+#pragma unroll
+                        for (int s = 0; s < 6; ++s) F[j][s] = make_float2(0.f, 0.f);
                 }
-                float2 o[6];
-                row_dft_part<NPARTS>(th + (g + NG * j) * TLD + t, v, o, scr, wt, t, xrd, h);
+            } else {
 #pragma unroll
-                for (int s = 0; s < 6; ++s) F[j][s] = h == hb ? o[s] : cadd(F[j][s], o[s]);
+                for (int j = 0; j < RPG; ++j) {
+                    if (!ron[j]) {
+#pragma unroll
+                        for (int s = 0; s < 6; ++s) F[j][s] = make_float2(0.f, 0.f);
+                        continue;
+                    }
+                    float2 o[6];
+                    row_dft_part<NPARTS>(th + C::row(g, j) * TLD + t, v, o, scr, wt, t, xrd, h);
+#pragma unroll
+                    for (int s = 0; s < 6; ++s) F[j][s] = h == hb ? o[s] : cadd(F[j][s], o[s]);
+                }
             }
             FPM_STAMP(8)
             // tail pixels: 16 lanes sum the part's TH terms; first half of the waves only
             for (int pp = g; g < NG / 2 && pp < a.n_tail_px; pp += NG / 2) {
                 const int2 px = tpx[pp];
                 const float2 *row = th + sig[px.x + KYOFF] * TLD;
-                // W^{x kx} for x = t + 16 m + TH h by recurrence over m (two
-                // table reads instead of eight bank-conflicting ones)
+                // W^{x kx} for x = xcol(t + 16 m) by recurrence over m (two
+                // table reads instead of eight bank-conflicting ones): x
+                // advances by 32 per m with two halves, by 16 with four parts
                 pf2 s2p = {0.f, 0.f};
-                pf2 wk = pin(tw[((t + TH * h) * (px.y + NP)) & (NP - 1)]);
-                const pf2 wstep = pin(tw[(16 * (px.y + NP)) & (NP - 1)]);
+                pf2 wk = pin(tw[(xcol(t) * (px.y + NP)) & (NP - 1)]);
+                const pf2 wstep = pin(tw[((PAIR ? 32 : 16) * (px.y + NP)) & (NP - 1)]);
 #pragma unroll
                 for (int m = 0; m < TH / 16; ++m) {
                     s2p += pmul(pin(row[t + 16 * m]), wk);

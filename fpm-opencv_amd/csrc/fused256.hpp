@@ -70,31 +70,6 @@ __device__ __forceinline__ void pdft16_out6(pf2 (&v)[16], pf2 (&o)[6]) {
     o[5] = psub_w4<INV>(v[12] - v[14], v[13] - v[15]);             // m = 15
 }
 
-// 16-point DFT whose input is zero outside v[8H .. 8H+7] (one half of a row)
-template <bool INV, int H>
-__device__ __forceinline__ void pdft16_inhalf(pf2 (&v)[16], pf2 (&r)[16]) {
-#pragma unroll
-    for (int k1 = 0; k1 < 4; ++k1) {
-        if (H == 0) {  // (a0, a1, 0, 0)
-            const pf2 a0 = v[k1], a1 = v[k1 + 4];
-            v[k1] = a0 + a1;
-            v[k1 + 4] = padd_w4<INV>(a0, a1);
-            v[k1 + 8] = a0 - a1;
-            v[k1 + 12] = psub_w4<INV>(a0, a1);
-        } else {       // (0, 0, a2, a3): W4^2 = -1, W4^3 = -W4
-            const pf2 a2 = v[k1 + 8], a3 = v[k1 + 12];
-            v[k1] = a2 + a3;
-            v[k1 + 4] = -padd_w4<INV>(a2, a3);
-            v[k1 + 8] = a2 - a3;
-            v[k1 + 12] = -psub_w4<INV>(a2, a3);
-        }
-    }
-    pmid_tw<INV>(v);
-    pstage2<INV>(v);
-#pragma unroll
-    for (int m = 0; m < 16; ++m) r[m] = v[4 * (m & 3) + (m >> 2)];
-}
-
 // first radix-4 butterfly of a 16-point DFT with one non-zero input a in
 // position Q of (k1, k1+4, k1+8, k1+12): a -> (a, W4^Q a, W4^2Q a, W4^3Q a)
 template <bool INV, int Q>
@@ -172,14 +147,15 @@ __device__ __forceinline__ void dft256_out6(float2 (&v)[16], float2 (&o)[6], flo
     from_pk(po, o);
 }
 
-// forward 256-point DFT of a half row (x = t + 16 n2, n2 in [8H, 8H+8), zero
-// elsewhere), output o[s] = X[t + 16 SK[s]]
-template <int H, class TW>
-__device__ __forceinline__ void dft256_inhalf_out6(float2 (&v)[16], float2 (&o)[6], float2 *scr, const TW &wt, int t,
-                                                   int xrd) {
+// forward 256-point DFT of quarter P of a row (x = t + 16 n2, n2 in
+// [4P, 4P+4), zero elsewhere), output o[s] = X[t + 16 SK[s]]
+template <int NPARTS, int P, class TW>
+__device__ __forceinline__ void dft256_inpart_out6(float2 (&v)[16], float2 (&o)[6], float2 *scr, const TW &wt,
+                                                   int t, int xrd) {
+    static_assert(NPARTS == 4, "four column parts (two halves run as row pairs, below)");
     pf2 pv[16], py[16], po[6];
     to_pk(v, pv);
-    pdft16_inhalf<false, H>(pv, py);
+    pdft16_inquarter<false, P>(pv, py);
     ptwiddle15<false>(py, wt);
     float2 y[16];
     from_pk(py, y);
@@ -187,28 +163,6 @@ __device__ __forceinline__ void dft256_inhalf_out6(float2 (&v)[16], float2 (&o)[
     to_pk(v, pv);
     pdft16_out6<false>(pv, po);
     from_pk(po, o);
-}
-
-// forward 256-point DFT of part P of NPARTS (x = t + 16 n2, n2 in
-// [P 16/NPARTS, (P+1) 16/NPARTS), zero elsewhere), output o[s] = X[t + 16 SK[s]]
-template <int NPARTS, int P, class TW>
-__device__ __forceinline__ void dft256_inpart_out6(float2 (&v)[16], float2 (&o)[6], float2 *scr, const TW &wt,
-                                                   int t, int xrd) {
-    if constexpr (NPARTS == 2) {
-        dft256_inhalf_out6<P>(v, o, scr, wt, t, xrd);
-    } else {
-        static_assert(NPARTS == 4, "two or four column parts");
-        pf2 pv[16], py[16], po[6];
-        to_pk(v, pv);
-        pdft16_inquarter<false, P>(pv, py);
-        ptwiddle15<false>(py, wt);
-        float2 y[16];
-        from_pk(py, y);
-        exchange16(scr, t, xrd, y, v);
-        to_pk(v, pv);
-        pdft16_out6<false>(pv, po);
-        from_pk(po, o);
-    }
 }
 
 // pruned forward row DFT of column part h (block-uniform, 0 <= h < NPARTS):
@@ -229,6 +183,165 @@ __device__ __forceinline__ void row_dft_part(const float2 *row, float2 (&v)[16],
         } else {
             row_dft_part<NPARTS, TW, HH + 1>(row, v, o, scr, wt, t, xrd, h);
         }
+    }
+}
+
+// ------------------------------------------------------------- row pairs
+// Blocks of the kernel with two column halves (fpm_fused.hip, NPARTS == 2):
+// the halves are cut on the LOW digit of the column, x = x1 + 16 x2 with half
+// H = x1 in [8H, 8H+8), so one four-step transform serves both FFT rows of a
+// group.  Spectral index k = kb + 16 ka; lane = low digit, register = high.
+//   inverse: lane kb forms, per row, the 8 stage-1 outputs x1 of the half
+//     (in-6, out-half DFT16 over ka), times W256^{-x1 kb}, into tile position
+//     8 j + (x1 - 8H); after the exchange lane t' holds the 16 kb of (row
+//     t' >> 3, x1 = 8H + (t' & 7)) and one dense DFT16 gives its 16 x2.
+//   forward: the mirror image; lane t' runs the dense DFT16 over x2, twiddles
+//     by W256^{x1 kb}, and after the exchange lane kb forms per row an
+//     in-half, out-6 DFT16 over x1.
+// tests/test_rowpair_model.py restates both with these index maps.
+
+// radix-4 butterfly returning outputs 2H and 2H+1 only; W2: a2 carries the
+// W16^4 mid twiddle (pbf4_w2)
+template <bool INV, int H, bool W2>
+__device__ __forceinline__ void pbf4_half(pf2 a0, pf2 a1, pf2 a2, pf2 a3, pf2 &lo, pf2 &hi) {
+    const pf2 s02 = W2 ? padd_w4<INV>(a0, a2) : a0 + a2, d02 = W2 ? psub_w4<INV>(a0, a2) : a0 - a2;
+    const pf2 s13 = a1 + a3, e13 = a1 - a3;
+    if constexpr (H == 0) {
+        lo = s02 + s13;
+        hi = padd_w4<INV>(d02, e13);
+    } else {
+        lo = s02 - s13;
+        hi = psub_w4<INV>(d02, e13);
+    }
+}
+
+// 16-point DFT of an input that is zero except in[s] at position SK[s],
+// returning the outputs m in [8H, 8H+8) as r[m - 8H]
+template <bool INV, int H>
+__device__ __forceinline__ void pdft16_in6_outhalf(const pf2 (&in)[6], pf2 (&r)[8]) {
+    const pf2 a0 = in[0], b1 = in[1], c2 = in[2], b13 = in[3], c14 = in[4], d15 = in[5];
+    const pf2 z = {0.f, 0.f};
+    pf2 v[16];  // stage 1 as pdft16_in6
+    v[0] = a0; v[4] = a0; v[8] = a0; v[12] = a0;
+    v[1] = b1 + b13;
+    v[5] = psub_w4<INV>(b1, b13);
+    v[9] = b1 - b13;
+    v[13] = padd_w4<INV>(b1, b13);
+    v[2] = c2 + c14;
+    v[6] = psub_w4<INV>(c2, c14);
+    v[10] = c2 - c14;
+    v[14] = padd_w4<INV>(c2, c14);
+    v[3] = d15;
+    v[7] = psub_w4<INV>(z, d15);
+    v[11] = -d15;
+    v[15] = padd_w4<INV>(z, d15);
+    pmid_tw<INV>(v);
+    // stage 2 over k1 for fixed m1: outputs m = m1 + 4 m2, m2 in {2H, 2H+1}
+    pbf4_half<INV, H, false>(v[0], v[1], v[2], v[3], r[0], r[4]);
+    pbf4_half<INV, H, false>(v[4], v[5], v[6], v[7], r[1], r[5]);
+    pbf4_half<INV, H, true>(v[8], v[9], v[10], v[11], r[2], r[6]);
+    pbf4_half<INV, H, false>(v[12], v[13], v[14], v[15], r[3], r[7]);
+}
+
+// 16-point DFT of an input that is zero outside positions 8H .. 8H+7 (in[i] at
+// 8H + i), returning the outputs m in SK as o[0..5]
+template <bool INV, int H>
+__device__ __forceinline__ void pdft16_inhalf_out6(const pf2 (&in)[8], pf2 (&o)[6]) {
+    pf2 v[16];
+#pragma unroll
+    for (int k1 = 0; k1 < 4; ++k1) {  // stage 1: two of a butterfly's four inputs
+        const pf2 a = in[k1], b = in[k1 + 4];
+        if (H == 0) {  // (a, b, 0, 0)
+            v[k1] = a + b;
+            v[k1 + 4] = padd_w4<INV>(a, b);
+            v[k1 + 8] = a - b;
+            v[k1 + 12] = psub_w4<INV>(a, b);
+        } else {       // (0, 0, a, b): W4^2 = -1, W4^3 = -W4
+            v[k1] = a + b;
+            v[k1 + 4] = -padd_w4<INV>(a, b);
+            v[k1 + 8] = a - b;
+            v[k1 + 12] = -psub_w4<INV>(a, b);
+        }
+    }
+    pmid_tw<INV>(v);
+    // stage 2 as pdft16_out6
+    o[0] = (v[0] + v[2]) + (v[1] + v[3]);
+    o[1] = (v[4] + v[6]) + (v[5] + v[7]);
+    o[2] = padd_w4<INV>(v[8], v[10]) + (v[9] + v[11]);
+    o[3] = psub_w4<INV>(v[4] - v[6], v[5] - v[7]);
+    o[4] = psub_w4<INV>(psub_w4<INV>(v[8], v[10]), v[9] - v[11]);
+    o[5] = psub_w4<INV>(v[12] - v[14], v[13] - v[15]);
+}
+
+// stage 1 of the paired inverse transform for half H: X[j][s] = X_j[t + 16 SK[s]]
+// of rows j = 0, 1 -> y[8 j + i] = W256^{-(8H+i) t} sum_ka X_j[t + 16 ka] W16^{-(8H+i) ka}
+// (wt: the lane's W256^{m t}; x1 = 0 has no twiddle)
+template <int H, class TW>
+__device__ __forceinline__ void idft256_pair_stage1(const float2 (&X)[2][6], pf2 (&py)[16], const TW &wt) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        pf2 in[6], o[8];
+        to_pk(X[j], in);
+        pdft16_in6_outhalf<true, H>(in, o);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) py[8 * j + i] = o[i];
+    }
+    pf2 w[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = pin(wt[8 * H + i]);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if constexpr (H == 0) {
+            ptw_block<true, 4>(&py[8 * j + 1], &w[1]);
+            ptw_block<true, 3>(&py[8 * j + 5], &w[5]);
+        } else {
+            ptw_block<true, 4>(&py[8 * j], &w[0]);
+            ptw_block<true, 4>(&py[8 * j + 4], &w[4]);
+        }
+    }
+}
+
+// inverse 256-point DFTs (unscaled) of the two rows of a group, column half h
+// (block-uniform): input X[j][s] = X_j[t + 16 SK[s]], output r[x2] =
+// x_j[x1 + 16 x2] for j = t >> 3, x1 = 8 h + (t & 7).  One unrolled branch
+// per half keeps every register index static.
+template <class TW>
+__device__ __forceinline__ void idft256_pair_in6(const float2 (&X)[2][6], float2 (&v)[16], float2 (&r)[16], float2 *scr,
+                                                 const TW &wt, int t, int xrd, int h) {
+    pf2 pv[16], py[16];
+    if (h == 0) idft256_pair_stage1<0>(X, py, wt);
+    else idft256_pair_stage1<1>(X, py, wt);
+    float2 y[16];
+    from_pk(py, y);
+    exchange16(scr, t, xrd, y, v);
+    to_pk(v, pv);
+    pdft16<true>(pv, py);
+    from_pk(py, r);
+}
+
+// forward 256-point DFTs of column half h of the two rows of a group: input
+// v[x2] = x_j[x1 + 16 x2] for j = t >> 3, x1 = 8 h + (t & 7), output o[j][s] =
+// the half's contribution to X_j[t + 16 SK[s]].  wx: W256^{m x1}, m = 0..15
+// (the twiddle set of the lane's x1, not of t).
+template <class TW>
+__device__ __forceinline__ void dft256_pair_out6(float2 (&v)[16], float2 (&o)[2][6], float2 *scr, const TW &wx, int t,
+                                                 int xrd, int h) {
+    pf2 pv[16], py[16];
+    to_pk(v, pv);
+    pdft16<false>(pv, py);
+    ptwiddle15<false>(py, wx);
+    float2 y[16];
+    from_pk(py, y);
+    exchange16(scr, t, xrd, y, v);
+    to_pk(v, pv);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        pf2 in[8], po[6];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) in[i] = pv[8 * j + i];
+        if (h == 0) pdft16_inhalf_out6<false, 0>(in, po);
+        else pdft16_inhalf_out6<false, 1>(in, po);
+        from_pk(po, o[j]);
     }
 }
 

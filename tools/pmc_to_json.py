@@ -46,12 +46,13 @@ def short(name):
     """Kernel key: the Np 256 fused kernels keep their template instance
     (k_fused_iteration<NT,KS>, k_fused_dist<KS>: workgroups per patch) so a
     profile of a split-mode instance is never read as the one-workgroup
-    kernel's."""
+    kernel's.  The key is the one bench.kernel_name looks up: further template
+    arguments (the gain flag) are dropped."""
     import re
-    m = re.search(r"k_fused_iteration<(\d+),\s*(\d+)>", name)
+    m = re.search(r"k_fused_iteration<(\d+),\s*(\d+)[,>]", name)
     if m:
         return f"k_fused_iteration<{m.group(1)},{m.group(2)}>"
-    m = re.search(r"k_fused_dist<(\d+)>", name)
+    m = re.search(r"k_fused_dist<(\d+)[,>]", name)
     if m:
         return f"k_fused_dist<{m.group(1)}>"
     for k in ("k_fused_mr", "k_fused_small", "k_fused_s90", "k_meas_layout", "k_meas_transpose_tiles", "k_meas_transpose",
