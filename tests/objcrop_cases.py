@@ -97,6 +97,12 @@ CONTEXTS = (
     Context("L3000", 2700, 3000, 4, 50, 2, BATCHED, "k_fft_batch C 2, radix 5", path=GENERAL, bands=BIG),
     Context("L90", 30, 90, 5, 4, 16, BATCHED, "k_fft_batch C 16, tail block of 10 sequences", path=GENERAL),
     Context("L96", 32, 96, 6, 4, 16, BATCHED, "k_fft_batch C 16", path=GENERAL),
+    # the C the capacity rule gives falls with L: 810 = 2 3^4 5 has C 8 and 2430 = 2 3^5 5 has C 4, each with a last
+    # block of 2 sequences; 5400 = 2^3 3^3 5^2 is the smallest L whose block holds one sequence
+    Context("L810", 30, 810, 5, 4, 8, BATCHED, "k_fft_batch C 8, tail block of 2 sequences", path=GENERAL),
+    Context("L2430", 30, 2430, 5, 4, 4, BATCHED, "k_fft_batch C 4, tail block of 2 sequences", path=GENERAL),
+    # 233 MB per array in complex64: two bands
+    Context("L5400", 30, 5400, 5, 4, 1, BATCHED, "k_fft_batch C 1", path=GENERAL, bands=("lo_hi", "straddle")),
     Context("L192", 64, 192, 10, 6, 16, BATCHED, "k_fft_batch C 16", path=GENERAL),
     Context("L96h", 32, 96, 6, 4, 16, BATCHED, "k_fft_batch C 16, fp16 input", flags=FP16),
     Context("L768h", 256, 768, 33, 24, 16, BATCHED, "k_fft_batch C 16, fp16 input", flags=FP16),

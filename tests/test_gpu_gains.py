@@ -52,7 +52,7 @@ from fpm_oracle import rel_l2
 from gain_cases import GAINCAL
 from test_gpu_probe import OFFSETS, PARITY, _entries
 from test_gpu_residual import BIN, GENERAL, _case, _context, _env, _solver
-from test_gpu_schedules import _check_maxima
+from maxima_check import check_maxima as _check_maxima
 from test_gpu_schedules import _solver as _case_solver
 
 pytestmark = pytest.mark.gpu

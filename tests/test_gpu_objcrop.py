@@ -14,7 +14,10 @@ Largest relative L2 measured on an MI355X, per context (all bands, all patches):
   L512 1.50e-7   L768 1.61e-7   L1024 1.57e-7   L600 1.69e-7   L360 1.54e-7
   L4096 1.80e-7  L4096h 1.73e-7  L4096b 1.38e-7  L3000 1.82e-7
   L90 1.37e-7    L96 1.31e-7    L192 1.40e-7    L96h 1.22e-7   L768h 1.48e-7
+  L810 1.68e-7   L2430 1.82e-7  L5400 1.51e-7
 The smallest, 6.2e-8, is L512 one_row; no case left an element not finite.
+The longest cases are the two of L 5400 (233 MB per array, one sequence per
+block of k_fft_batch): 0.7 s each, most of it the complex128 reference.
 """
 import ctypes
 

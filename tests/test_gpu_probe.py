@@ -35,7 +35,7 @@ from fpm_amd import calibrate
 from fpm_oracle import rel_l2
 from test_gpu_residual import (BIN, COLS, FUSED, G_LDS, G_REG256, G_REG1024, GENERAL, NP256_KERNELS, R_LDS, R_REG, _case,
                                _context, _env, _plan, _solver)
-from test_gpu_schedules import _check_maxima
+from maxima_check import check_maxima as _check_maxima
 from test_probe import CALIB, float64_decisions, float64_tables, window_reference
 from tools.synth import make_stack
 
@@ -285,7 +285,7 @@ def test_set_crops_is_create(name):
 
 
 class _Band:
-    """What test_gpu_schedules._check_maxima reads of a case: the row and the live band."""
+    """What maxima_check.check_maxima reads of a case: the row and the live band."""
 
     def __init__(self, row, band):
         self.row, self._band = row, band

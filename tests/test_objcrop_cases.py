@@ -23,7 +23,12 @@ IDS = [oc.case_id(c, b) for c, b in CASES]
 
 def test_table_shape():
     assert BOUND == 2e-6
-    assert len(CASES) == 10 * 7 + 3 * 4 + 1
+    assert len(CASES) == 12 * 7 + 3 * 4 + 1 + 2
+    assert oc.BY_ID["L5400"].bands == ("lo_hi", "straddle")
+    assert [oc.BY_ID[k].n_patch("straddle") for k in ("L810", "L2430", "L5400")] == [2, 1, 1]
+    for k in ("L810", "L2430", "L5400"):
+        c = oc.BY_ID[k]
+        assert (c.Np, c.r, c.step, c.family, c.path) == (30, 5, 4, BATCHED, oc.GENERAL)
     assert {c.id for c in oc.CONTEXTS if c.bands == oc.BIG} == {"L4096", "L4096h", "L3000"}
     assert oc.BY_ID["L4096b"].bands == ("straddle",)
     for ctx, name in CASES:
@@ -86,31 +91,58 @@ def live_rows_per_block(ctx, sy0, sy1):
 def test_rows_per_block_are_the_tables():
     for ctx in oc.CONTEXTS:
         assert rows_per_block(ctx) == ctx.Gr, ctx.id
-    assert [batched_C(L) for L in (4096, 3000, 90, 96, 192, 768)] == [2, 2, 16, 16, 16, 16]
+    assert [batched_C(L) for L in (4096, 3000, 90, 96, 192, 768, 810, 2430, 5400)] == [2, 2, 16, 16, 16, 16, 8, 4, 1]
     assert 5 in radices(3000) and 5 in radices(90)
+    assert radices(810) == [2, 3, 3, 3, 3, 5] and radices(2430) == [2, 3, 3, 3, 3, 3, 5]
+    assert radices(5400) == [8, 3, 3, 3, 5, 5]
+    # the first even 5-smooth L of each (C, L mod C): C 8 starts at 720 and C 4 at 1350; 810 is the first C 8 whose
+    # last block holds 2 sequences, and no L below 5400 has a block of one sequence
+    first = {}
+    for L in range(2, 5401, 2):
+        try:
+            first.setdefault((batched_C(L), L % batched_C(L)), L)
+        except AssertionError:      # not 5-smooth
+            pass
+    assert (first[8, 0], first[8, 2], first[4, 2], first[1, 0]) == (720, 810, 1350, 5400)
+    assert min(k[0] for k in first) == 1
+
+
+# H mod C sequences of lo_hi / hi_lo lie before the first block boundary: 45 mod 16 = 13, 405 mod 8 = 5, 1215 mod 4 = 3
+UNALIGNED = {"L90": {"lo_hi": [3, 14], "hi_lo": [3, 16, 13], "one_row": [1]},
+             "L810": {"lo_hi": [3, 6], "hi_lo": [3, 8, 5], "one_row": [1]},
+             "L2430": {"lo_hi": [1, 4], "hi_lo": [1, 4, 3], "one_row": [1]}}
 
 
 @pytest.mark.parametrize("ctx", [c for c in oc.CONTEXTS if c.family != C4K], ids=lambda c: c.id)
 def test_block_edges(ctx):
     """lo_hi: a full block and a tail block with exactly one live row; hi_lo:
-    exactly two full blocks; one_row: one live row.  L 90 is the exception:
-    its blocks of 16 sequences are not aligned with H = 45, so lo_hi's 17 rows
-    fall 3 + 14 into two partly live blocks -- the tail block that L 90 is
-    here for is the launch's own (test_l90_tail_block)."""
+    exactly two full blocks; one_row: one live row.  L 90, 810 and 2430 are the
+    exceptions: their blocks of C sequences are not aligned with H = L / 2, so
+    lo_hi's C + 1 rows (L 90: 17 = 3 + 14) and hi_lo's 2 C fall into partly
+    live blocks -- the tail block these sizes are here for is the launch's own
+    (test_l90_tail_block)."""
     G = ctx.Gr
     for name, want in (("lo_hi", [G, 1]), ("hi_lo", [G, G]), ("one_row", [1])):
         if name not in (ctx.bands or oc.BANDS):
             continue
         sy0, sy1, _, _ = oc.band(ctx, name)
         got = live_rows_per_block(ctx, sy0, sy1)
-        if ctx.id == "L90":
-            want = {"lo_hi": [3, 14], "hi_lo": [3, 16, 13], "one_row": [1]}[name]
+        if ctx.id in UNALIGNED:
+            want = UNALIGNED[ctx.id][name]
         assert got == want, (ctx.id, name, got)
 
 
 def test_l90_tail_block():
     C = batched_C(90)
     assert C == 16 and -(-90 // C) == 6 and 90 - 5 * C == 10     # cs = min(C, nseq - s0) = 10 in the last block
+    C = batched_C(810)
+    assert C == 8 and -(-810 // C) == 102 and 810 - 101 * C == 2       # C 8: cs = 2
+    C = batched_C(2430)
+    assert C == 4 and -(-2430 // C) == 608 and 2430 - 607 * C == 2     # C 4: cs = 2
+    assert batched_C(5400) == 1                                          # C 1: every block is full
+    # full bands reach the tail block: its sequences are objF rows L - 2 and L - 1
+    for cid in ("L810", "L2430"):
+        assert "full" in (oc.BY_ID[cid].bands or oc.BANDS)
 
 
 @pytest.mark.parametrize("cid,pieces", [("L512", 2), ("L768", 2), ("L1024", 2), ("L600", 2)])
@@ -156,7 +188,7 @@ def test_edges_of_the_spectrum_are_reached():
 C128_BANDS_4096 = {"L4096": "lo_hi", "L4096h": "upper_only", "L4096b": "straddle"}
 
 
-@pytest.mark.parametrize("ctx,name", [(c, b) for c, b in CASES if c.L < 4096 or C128_BANDS_4096[c.id] == b],
+@pytest.mark.parametrize("ctx,name", [(c, b) for c, b in CASES if C128_BANDS_4096.get(c.id, b) == b],
                          ids=lambda v: v.id if isinstance(v, oc.Context) else v)
 def test_fp32_headroom_and_distinct_patches(ctx, name):
     spec = oc.make_input(ctx, name)
