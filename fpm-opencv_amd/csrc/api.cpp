@@ -166,7 +166,7 @@ int fpm_debug_objcrop(fpm_ctx *c, const float *spec, const int band[4], float *o
         HIP_TRY(hipMemcpy(st.spec, spec, n * sizeof(float2), hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMemsetAsync(c->objcrop, 0xFF, n * sizeof(float2), c->stream));
-    HIP_TRY(launch_objcrop(st, c->objcrop, c->pl_L, c->tw_L, c->sw, c->stream));
+    HIP_TRY(launch_objcrop(c->oplan, st, c->objcrop, c->tw_L, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(objcrop, c->objcrop, n * sizeof(float2), hipMemcpyDeviceToHost));
     return FPM_OK;

@@ -204,9 +204,9 @@ void plan_state(fpm_ctx *c, const DevState *keep) {
 // a planned launch within the LDS a workgroup can have (dynamic plus the kernel's own)
 int lds_fits(const fpm_ctx *c, const char *what, const StepKernel &k, size_t lds_limit) {
     if (k.lds_total() <= lds_limit) return FPM_OK;
-    return set_err(FPM_ERR_INVAL, "Np=%d r=%d: the %s kernel needs %zu B of LDS (%zu dynamic + %zu static), the "
-                   "device offers %zu", c->prob.np, c->prob.na_radius, what, k.lds_total(), k.lds, k.lds_static,
-                   lds_limit);
+    return set_err(FPM_ERR_INVAL, "Np=%d r=%d Nlarge=%d: the %s kernel needs %zu B of LDS (%zu dynamic + %zu static), "
+                   "the device offers %zu", c->prob.np, c->prob.na_radius, c->prob.nlarge, what, k.lds_total(), k.lds,
+                   k.lds_static, lds_limit);
 }
 
 // the sweep's LDS pair (the register pair's LDS does not grow with the problem)
@@ -216,12 +216,31 @@ int residual_lds_fits(const fpm_ctx *c, size_t lds_limit) {
     return rc ? rc : lds_fits(c, "residual column", c->rplan.cols, lds_limit);
 }
 
+// objCrop's launches: only the batched transform's LDS grows with the problem
+// (Nlarge 10240: DESIGN.md section 4.7)
+int objcrop_lds_fits(const fpm_ctx *c, size_t lds_limit) {
+    const ObjcropPlan &p = c->oplan;
+    if (!p.rows.fn)
+        return set_err(FPM_ERR_INVAL, "Nlarge=%d: not one sequence fits a block of the batched transform",
+                       c->prob.nlarge);
+    int rc = lds_fits(c, "objCrop row", p.rows, lds_limit);
+    if (!rc) rc = lds_fits(c, "objCrop column", p.cols, lds_limit);
+    if (!rc && p.kind == ObjcropPlan::SixStep4k) rc = lds_fits(c, "objCrop second column", p.cols2, lds_limit);
+    return rc;
+}
+
+// the last checks of every plan: the residual sweep's launches, then objCrop's
+int sweep_and_objcrop_fit(const fpm_ctx *c, size_t lds_limit) {
+    const int rc = residual_lds_fits(c, lds_limit);
+    return rc ? rc : objcrop_lds_fits(c, lds_limit);
+}
+
 // Everything a context is, decided from the validated problem (c->prob with
 // its arrays), the switches (c->sw), the device's CU count and its LDS per
 // workgroup before anything is created: no HIP call, no device memory.
 // Refuses a fused path that this geometry or fp16 spectrum storage does not
-// have, and a size whose planned step or sweep kernel needs more LDS than the
-// device offers (Np 10240: DESIGN.md section 4.7).
+// have, and a size whose planned step, sweep or objCrop kernel needs more LDS
+// than the device offers (Np 10240, Nlarge 10240: DESIGN.md section 4.7).
 int plan_context(fpm_ctx *c, int n_cu, size_t lds_limit, const DevState *keep = nullptr) {
     const fpm_problem &p = c->prob;
     const Switches &sw = c->sw;
@@ -241,6 +260,7 @@ int plan_context(fpm_ctx *c, int n_cu, size_t lds_limit, const DevState *keep = 
         }
 
     const bool fp16 = (p.flags & FPM_FLAG_SPEC_FP16) != 0;
+    c->oplan = plan_objcrop(L, fp16, c->pl_L, sw);
     // Np 90 (configs 1 / 2): the register-transform kernel unless FPM_NO_S90=1
     // selects the generic small-patch kernel
     const Kernel fused = fused_threads(np, r, L, st)                                  ? Kernel::Np256
@@ -265,7 +285,7 @@ int plan_context(fpm_ctx *c, int n_cu, size_t lds_limit, const DevState *keep = 
         st.npart = 1;
         c->meas_g = c->row().meas_g < 0 ? np : c->row().meas_g;
         c->rplan = plan_residual(st, c->pl_np, p.n_order, c->meas_g, fp16, sw);
-        return residual_lds_fits(c, lds_limit);
+        return sweep_and_objcrop_fit(c, lds_limit);
     }
     // Np 1024 general path: register row/column kernels reading the stack
     // transposed; Np 256 beyond the fused kernels' radius: register kernels
@@ -304,7 +324,7 @@ int plan_context(fpm_ctx *c, int n_cu, size_t lds_limit, const DevState *keep = 
             (rc = lds_fits(c, "row DFT / update", gp.k3, lds_limit)))
             return rc;
     }
-    return residual_lds_fits(c, lds_limit);
+    return sweep_and_objcrop_fit(c, lds_limit);
 }
 
 // the run stream, the buffers and the patch groups' streams the plan names
@@ -472,6 +492,8 @@ int fpm_create(const fpm_problem *prob, int device, fpm_ctx **out) {
     if (!c->fused())
         for (int g = 0; g < c->ngroups && c->general_kind == GeneralPlan::Lds; ++g)
             HIP_TRY(allow_large_lds({&c->gplan[g].k1, &c->gplan[g].k2, &c->gplan[g].k3, &c->gplan[g].k3_gain}, lds_limit));
+    // the register column passes of L 1024, 600 and 360; launch_fft_batch sets its own
+    if (c->oplan.regs()) HIP_TRY(allow_large_lds({&c->oplan.rows, &c->oplan.cols}, lds_limit));
     *out = c.release();
     return FPM_OK;
 }
@@ -618,6 +640,35 @@ int fpm_debug_plan_ladder(int np, int nb, int B, int step, int no_wave_cols, int
     }
     out->rows = ladder_kernel(rows, l.row_e, 0, row_static);
     out->cols = ladder_kernel(cols, l.col_e, l.cw, cols.lds_static);
+    return FPM_OK;
+}
+
+static void fill_objcrop_plan(const ObjcropPlan &p, fpm_objcrop_plan *out) {
+    out->kind = p.regs() ? (p.kind == ObjcropPlan::Regs256M ? FPM_OBJCROP_REGS_256M
+                            : p.kind == ObjcropPlan::Regs600 ? FPM_OBJCROP_REGS_600 : FPM_OBJCROP_REGS_360)
+                : p.kind == ObjcropPlan::SixStep4k ? FPM_OBJCROP_SIX_STEP_4K : FPM_OBJCROP_BATCHED;
+    out->per_block = p.first().arg;
+    out->rows_lds_dynamic = (int)p.rows.lds;
+    out->rows_lds_static = (int)p.rows.lds_static;
+    out->cols_lds_dynamic = (int)p.cols.lds;
+    out->cols_lds_static = (int)p.cols.lds_static;
+}
+
+int fpm_debug_plan_objcrop(int nlarge, int fp16, int no_crop4k, fpm_objcrop_plan *out) {
+    if (!out || nlarge < 4 || (nlarge & 1)) return set_err(FPM_ERR_INVAL, "fpm_debug_plan_objcrop: bad argument");
+    FftPlan pl;
+    if (!make_plan(nlarge, &pl)) return set_err(FPM_ERR_INVAL, "Nlarge=%d is not 2^a 3^b 5^c", nlarge);
+    if (nlarge > fft_max_len())  // as validate()
+        return set_err(FPM_ERR_INVAL, "Nlarge=%d exceeds the batched transform limit %d", nlarge, fft_max_len());
+    Switches sw{};
+    sw.no_crop4k = no_crop4k != 0;
+    fill_objcrop_plan(plan_objcrop(nlarge, fp16 != 0, pl, sw), out);
+    return FPM_OK;
+}
+
+int fpm_debug_get_objcrop_plan(const fpm_ctx *c, fpm_objcrop_plan *out) {
+    if (!c || !out) return set_err(FPM_ERR_INVAL, "null argument");
+    fill_objcrop_plan(c->oplan, out);
     return FPM_OK;
 }
 

@@ -95,6 +95,8 @@ struct fpm_ctx {
     int ngroups = 1;
     static constexpr int kMaxGroups = 8;
     fpm::ResidualPlan rplan{};      // fpm_residual: kernel pair and LEDs per launch
+    fpm::ObjcropPlan oplan{};       // objCrop: which transform and its launches (plan_objcrop); the crop table
+                                    // changes the band its grids follow, never the plan
     // ---- what the context owns
     hipStream_t stream = nullptr;   // the run stream: own_stream or the caller's (fpm_set_stream)
     hipStream_t own_stream = nullptr;

@@ -1,6 +1,6 @@
 // dft16.hpp -- register-resident 16-point DFTs and the 16x16 four-step
 // exchange shared by the fused LED-update kernel (fpm_fused.hip) and the
-// objCrop transform (objcrop.hip).
+// objCrop transform (crop256m.hip).
 //
 // Layout: a 16-lane group holds 16 complex values per lane; a 256-point
 // transform is two register 16-point DFTs with one LDS exchange between them.

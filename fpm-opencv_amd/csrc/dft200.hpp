@@ -1,6 +1,6 @@
 // dft200.hpp -- register-resident 200-point DFT of a 10-lane group (20 x 10
 // four-step, packed FP32), shared by the Np 200 fused LED-update kernel
-// (fused_mr.hip) and the L = 600 objCrop transform (objcrop.hip).
+// (fused_mr.hip) and the L = 600 objCrop transform (crop600.hip).
 //
 //   lane l holds x[l + 10 k], k = 0..19 (the "slot layout").  Stage 1 is a
 //   20-point DFT over the registers (5 x 4), then the twiddles W200^{l m1}, one

@@ -1,7 +1,7 @@
 // dftL.hpp -- L = 256*M point transforms (M = 2, 3, 4) held entirely in the
 // registers of one 16-lane group: M four-step 256-point DFTs (dft16.hpp) of
 // the stride-M sub-sequences, then a lane-local radix-M combine.  Shared by
-// the objCrop transform (objcrop.hip) and the Np 1024 row/column kernels of
+// the objCrop transform (crop256m.hip) and the Np 1024 row/column kernels of
 // the general path (np1024.hip).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -109,18 +109,28 @@ static int fft_log2_seq_per_block(const FftPlan &pl) {
 
 int fft_max_len() { return fft_pass_capacity(5); }  // the smallest of the radix-2/3/4/5 capacities
 
+StepKernel fft_batch_kernel(const FftPlan &pl, bool inverse) {
+    StepKernel k{};
+    const int lc = fft_log2_seq_per_block(pl);
+    if (lc < 0) return k;
+    k.fn = inverse ? (const void *)k_fft_batch<true> : (const void *)k_fft_batch<false>;
+    k.block = dim3(kFftThreads);
+    // row-major tiles carry one pad element per sequence
+    k.lds = (((size_t)1 << lc) * (pl.n + 1) + pl.n) * sizeof(float2);  // tile + twiddles
+    k.arg = lc;
+    return k;
+}
+
 hipError_t launch_fft_batch(bool inverse, const float2 *in, float2 *out, const FftPlan &pl, const float2 *tw,
                             int nseq, int B, size_t in_bs, int in_ss, int in_es, size_t out_bs, int out_ss,
                             int out_es, int sroll, int iroll, float scale, hipStream_t s, const __half2 *in16,
                             float in16_scale, FftBand band) {
-    const int lc = fft_log2_seq_per_block(pl);
-    if (lc < 0) return hipErrorInvalidValue;
-    const int C = 1 << lc;
-    // row-major tiles carry one pad element per sequence
-    const size_t lds = ((size_t)C * (pl.n + 1) + pl.n) * sizeof(float2);  // tile + twiddles
+    const StepKernel k = fft_batch_kernel(pl, inverse);
+    if (!k.fn) return hipErrorInvalidValue;
+    const int lc = k.arg, C = 1 << lc;
+    const size_t lds = k.lds;
     dim3 grid((nseq + C - 1) / C, B);
-    hipError_t e = hipFuncSetAttribute(inverse ? (const void *)k_fft_batch<true> : (const void *)k_fft_batch<false>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     if (inverse)
         hipLaunchKernelGGL(k_fft_batch<true>, grid, dim3(kFftThreads), lds, s, in, out, pl, tw, lc, nseq, in_bs,

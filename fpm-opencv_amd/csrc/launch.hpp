@@ -177,16 +177,58 @@ struct FftBand {
     int qlo = 0, qhi = 0x7fffffff, elo = 0, ehi = 0x7fffffff, eroll = 0;
 };
 int fft_max_len();
+// The launch of k_fft_batch for a length: fn (null when not even one sequence
+// fits a block), the block, the dynamic LDS of the tile and the twiddles and
+// arg = lc, log2 of the sequences per block.  What launch_fft_batch launches
+// and what plan_objcrop records.
+StepKernel fft_batch_kernel(const FftPlan &pl, bool inverse);
 hipError_t launch_fft_batch(bool inverse, const float2 *in, float2 *out, const FftPlan &pl, const float2 *tw,
                             int nseq, int B, size_t in_bs, int in_ss, int in_es, size_t out_bs, int out_ss,
                             int out_es, int sroll, int iroll, float scale, hipStream_t s,
                             const __half2 *in16 = nullptr, float in16_scale = 1.f, FftBand band = FftBand());
 
-// ---- fpm_init (init.hip) and objCrop (objcrop.hip)
+// ---- fpm_init (init.hip)
 hipError_t launch_init(const DevState &st, int init_led, float2 *scratch, const FftPlan &pl_np,
                        const float2 *tw_np, hipStream_t s);
-hipError_t launch_objcrop(const DevState &st, float2 *out, const FftPlan &pl_L, const float2 *tw_L,
-                          const Switches &sw, hipStream_t s);
+
+// ---- objCrop (objcrop.hip; kernels: crop256m.hip, crop600.hip, crop360.hip, crop4k.hip, fft_batch.hip)
+// The two launches of a register family, one table row per family file.  Every
+// row kernel takes (spec, out, tw, sy0, sy1, sx0, sx1) and every column kernel
+// (io, tw, scale, sy0, sy1); arg = rows per block / columns per strip.  The
+// grids follow the live band, which fpm_set_crops and fpm_debug_objcrop
+// change, so they are computed at launch.
+struct CropPair {
+    StepKernel rows, cols;  // grid unset
+};
+inline StepKernel crop_kernel(const void *fn, int threads, size_t lds, int per_block, size_t lds_static = 0) {
+    return StepKernel{fn, dim3(), dim3(threads), lds, per_block, lds_static};
+}
+CropPair crop256m_kernels(int L);  // L = 512 / 768 / 1024; any other L: fn null
+CropPair crop600_kernels();
+CropPair crop360_kernels();
+// The three passes of the six-step L 4096 transform, in launch order; arg =
+// columns (cols1, cols2) / rows per block
+struct Crop4kKernels {
+    StepKernel cols1, cols2, rows;  // grid unset
+};
+Crop4kKernels crop4k_kernels();
+// What launch_objcrop launches for a context; decided with the rest of the
+// context (plan_context: no HIP call).
+struct ObjcropPlan {
+    // register transforms of L = 256 M, 600 and 360; the six-step L 4096
+    // passes; the batched transform (fft_batch.hip)
+    enum Kind { Regs256M, Regs600, Regs360, SixStep4k, Batched } kind;
+    StepKernel rows, cols;  // grid unset; Batched: k_fft_batch, arg = sequences per block C (fn null: L does not fit)
+    StepKernel cols2;       // SixStep4k only: the in-place second column pass (cols is the first)
+    FftPlan pl;             // Batched only: of L
+    bool regs() const { return kind == Regs256M || kind == Regs600 || kind == Regs360; }
+    // the pass that runs first: the six-step transform starts with its columns
+    const StepKernel &first() const { return kind == SixStep4k ? cols : rows; }
+};
+ObjcropPlan plan_objcrop(int L, bool fp16, const FftPlan &pl_L, const Switches &sw);
+// hipErrorInvalidValue when the live band of st is not 0 <= lo <= hi < L
+hipError_t launch_objcrop(const ObjcropPlan &plan, const DevState &st, float2 *out, const float2 *tw_L,
+                          hipStream_t s);
 
 // ---- Np 256 fused kernel: one workgroup per patch and split mode (fpm_fused.hip)
 int fused_threads(int np, int r, int L, const DevState &st);

@@ -10,7 +10,7 @@
 using namespace fpm;
 
 int fpm::refresh_objcrop(fpm_ctx *c) {
-    HIP_TRY(launch_objcrop(c->st, c->objcrop, c->pl_L, c->tw_L, c->sw, c->stream));
+    HIP_TRY(launch_objcrop(c->oplan, c->st, c->objcrop, c->tw_L, c->stream));
     c->objcrop_valid = true;
     return FPM_OK;
 }

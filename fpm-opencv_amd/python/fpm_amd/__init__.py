@@ -54,9 +54,12 @@ HIP_SYMBOLS = (
 )
 # test-only entry points (include/fpm_hip_debug.h)
 HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan",
-                     "fpm_debug_get_maxima", "fpm_debug_plan_ladder", "fpm_debug_get_ladder", "fpm_debug_objcrop")
+                     "fpm_debug_get_maxima", "fpm_debug_plan_ladder", "fpm_debug_get_ladder", "fpm_debug_objcrop",
+                     "fpm_debug_plan_objcrop", "fpm_debug_get_objcrop_plan")
 # fpm_ladder_kernel.generation
 LADDER_ONE_SEQ, LADDER_TILED, LADDER_WAVE = 0, 1, 2
+# fpm_objcrop_plan.kind
+OBJCROP_REGS_256M, OBJCROP_REGS_600, OBJCROP_REGS_360, OBJCROP_SIX_STEP_4K, OBJCROP_BATCHED = 0, 1, 2, 3, 4
 # fpm_debug_get_plan: general_kind / residual_kind values
 GENERAL_REG1024, GENERAL_REG256, GENERAL_LDS = 0, 1, 2
 RESIDUAL_REG256, RESIDUAL_LDS = 0, 1
@@ -126,6 +129,14 @@ class fpm_ladder(C.Structure):
         return dict(rows=self.rows.as_dict(), cols=self.cols.as_dict())
 
 
+class fpm_objcrop_plan(C.Structure):
+    _fields_ = [("kind", C.c_int), ("per_block", C.c_int), ("rows_lds_dynamic", C.c_int), ("rows_lds_static", C.c_int),
+                ("cols_lds_dynamic", C.c_int), ("cols_lds_static", C.c_int)]
+
+    def as_dict(self):
+        return {f: int(getattr(self, f)) for f, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -161,6 +172,8 @@ def load_library(path: str = HIP_LIB):
         "fpm_debug_plan_ladder": (C.c_int, [C.c_int] * 6 + [C.POINTER(fpm_ladder)]),
         "fpm_debug_get_ladder": (C.c_int, [vp, C.c_int, C.POINTER(fpm_ladder)]),
         "fpm_debug_objcrop": (C.c_int, [vp, f32p, C.POINTER(C.c_int), f32p]),
+        "fpm_debug_plan_objcrop": (C.c_int, [C.c_int] * 3 + [C.POINTER(fpm_objcrop_plan)]),
+        "fpm_debug_get_objcrop_plan": (C.c_int, [vp, C.POINTER(fpm_objcrop_plan)]),
         "fpm_get_timing": (C.c_int, [vp, C.POINTER(fpm_timing)]),
         "fpm_get_clock": (C.c_int, [vp, C.POINTER(fpm_clock)]),
         "fpm_residual": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -481,6 +494,13 @@ class Solver:
         _check(_lib.fpm_debug_get_ladder(self._h, int(residual), C.byref(l)))
         return l.as_dict()
 
+    def debug_objcrop_plan(self) -> dict:
+        """Test-only (include/fpm_hip_debug.h): what the context's objCrop
+        launches, as debug_plan_objcrop returns it."""
+        o = fpm_objcrop_plan()
+        _check(_lib.fpm_debug_get_objcrop_plan(self._h, C.byref(o)))
+        return o.as_dict()
+
     def debug_objcrop(self, spec, band) -> np.ndarray:
         """Test-only (include/fpm_hip_debug.h): objCrop of the CENTRED spectrum
         `spec`, complex64 [n_patch][L][L], with the live band (sy0, sy1, sx0, sx1)
@@ -522,6 +542,16 @@ def debug_plan_ladder(np_: int, nb: int, B: int, step: bool = True, no_wave_cols
     _check(lib.fpm_debug_plan_ladder(int(np_), int(nb), int(B), int(step), int(no_wave_cols), int(one_seq),
                                      C.byref(l)))
     return l.as_dict()
+
+
+def debug_plan_objcrop(L: int, fp16: bool = False, no_crop4k: bool = False) -> dict:
+    """Test-only (include/fpm_hip_debug.h): what the objCrop planner picks for
+    Nlarge = L: kind (OBJCROP_*), per_block, and the dynamic / static LDS bytes
+    of the row and column launches.  Needs no GPU."""
+    lib = load_library()
+    o = fpm_objcrop_plan()
+    _check(lib.fpm_debug_plan_objcrop(int(L), int(fp16), int(no_crop4k), C.byref(o)))
+    return o.as_dict()
 
 
 def normalised_residual(d) -> np.ndarray:

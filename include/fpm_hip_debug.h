@@ -92,9 +92,36 @@ int fpm_debug_plan_ladder(int np, int nb, int B, int step, int no_wave_cols, int
  * they differ. */
 int fpm_debug_get_ladder(const fpm_ctx *ctx, int residual, fpm_ladder *out);
 
+/* What plan_objcrop (objcrop.hip) decides for a spectrum size: the transform
+ * objCrop runs and the launches of its row and column passes. */
+#define FPM_OBJCROP_REGS_256M 0   /* register transforms of L = 512 / 768 / 1024 (crop256m.hip) */
+#define FPM_OBJCROP_REGS_600 1    /* of L 600 (crop600.hip) */
+#define FPM_OBJCROP_REGS_360 2    /* of L 360 (crop360.hip) */
+#define FPM_OBJCROP_SIX_STEP_4K 3 /* the six-step passes of L 4096 (crop4k.hip) */
+#define FPM_OBJCROP_BATCHED 4     /* k_fft_batch (fft_batch.hip) */
+typedef struct fpm_objcrop_plan {
+    int kind;             /* FPM_OBJCROP_* */
+    int per_block;        /* what a block of the first pass holds: rows of the live band (register kinds),
+                             sequences C (batched), columns (six-step: its column passes run first) */
+    int rows_lds_dynamic; /* bytes the row launch asks for */
+    int rows_lds_static;  /* bytes of the row kernel's own __shared__ arrays */
+    int cols_lds_dynamic; /* the same of the column launch (six-step: of its first column pass) */
+    int cols_lds_static;
+} fpm_objcrop_plan;
+
+/* The plan for Nlarge = nlarge, with fp16 spectrum storage (fp16 != 0:
+ * FPM_FLAG_SPEC_FP16) and the switch FPM_NO_CROP4K (no_crop4k != 0).  Calls
+ * the planner itself and nothing of HIP: needs neither a context nor a device,
+ * and does not compare the LDS with any device's limit.  FPM_ERR_INVAL when
+ * nlarge is odd, below 4, not 2^a 3^b 5^c or beyond the batched transform. */
+int fpm_debug_plan_objcrop(int nlarge, int fp16, int no_crop4k, fpm_objcrop_plan *out);
+
+/* The same record of a live context: what its fpm_run and fpm_debug_objcrop launch. */
+int fpm_debug_get_objcrop_plan(const fpm_ctx *ctx, fpm_objcrop_plan *out);
+
 /* objCrop of a given spectrum and live band, through the product's own
- * launch_objcrop (objcrop.hip, fft_batch.hip): no kernel and no dispatch of
- * its own.  Legal on any created context; needs neither a stack nor fpm_init.
+ * launch_objcrop with the context's plan (objcrop.hip and the kernel files it
+ * names): no kernel and no dispatch of its own.  Legal on any created context; needs neither a stack nor fpm_init.
  *   spec    [B][L][L][2]  the CENTRED spectrum, copied verbatim into the
  *                         context's spectrum buffer (FPM_FLAG_SPEC_FP16: stored
  *                         as half(v * hscale), as every kernel stores it)

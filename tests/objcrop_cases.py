@@ -1,9 +1,12 @@
 """Case table of the objCrop tests: plain data and builders, no GPU.
 
 objCrop = IDFT2(fftShift(spec)) / L^2 runs on one of six kernel families
-(csrc/objcrop.hip launch_objcrop, csrc/fft_batch.hip), and each skips
-everything outside the live band [sy0, sy1] x [sx0, sx1] of the centred
-spectrum.  A context (CONTEXTS) selects the family; a band (BANDS) is a shape
+(csrc/objcrop.hip plan_objcrop and launch_objcrop; the kernels in
+csrc/crop256m.hip, crop600.hip, crop360.hip, crop4k.hip and fft_batch.hip), and
+each skips everything outside the live band [sy0, sy1] x [sx0, sx1] of the
+centred spectrum.  A context (CONTEXTS) selects the family -- asserted from
+the library's planner (tests/test_objcrop_cases.py) and from each live
+context's plan (tests/test_gpu_objcrop.py); a band (BANDS) is a shape
 the launchers accept (0 <= lo <= hi < L) whether or not an LED geometry could
 plan it.  fpm_debug_objcrop (Solver.debug_objcrop) runs the context's own
 launch on a given spectrum and band.
@@ -54,7 +57,7 @@ class Context:
     step: int                   # of the 3 x 3 LED grid
     Gr: int                     # rows per block of the row pass (batched: sequences per block C)
     family: str
-    kernel: str                 # what launch_objcrop reaches
+    kernel: str                 # what the context's objCrop plan launches
     flags: int = 0
     path: int = fpm_amd.PATH_AUTO
     env: dict = field(default_factory=dict)   # environment at fpm_create

@@ -142,6 +142,20 @@ def test_create_refuses_np10240():
     assert e.value.code == fpm_amd.FPM_ERR_INVAL and "Np=10240" in str(e.value)
 
 
+def test_create_refuses_nlarge10240():
+    """Nlarge 10240: objCrop's batched transform holds one sequence per block
+    and asks for (10241 + 10240) * 8 = 163 848 B of LDS, 8 more than a workgroup
+    can have.  plan_context refuses before anything is allocated; the step and
+    the sweep of Np 32 fit."""
+    from tools.synth import grid_geometry
+    Np, L, r = 32, 10240, 6
+    x0, y0, order = grid_geometry(Np, L, 3, 4)
+    prob = fpm_amd.Problem(Np, L, order, x0, y0, r, 5, 10, n_patch=1)
+    with pytest.raises(fpm_amd.FpmError, match="LDS") as e:
+        fpm_amd.Solver(prob)
+    assert e.value.code == fpm_amd.FPM_ERR_INVAL and "10240" in str(e.value) and "objCrop" in str(e.value)
+
+
 def test_get_ladder_refuses_fused_and_register_contexts():
     from tools.synth import grid_geometry
     for Np, L, r, path in ((256, 512, 33, fpm_amd.PATH_FUSED), (256, 512, 40, fpm_amd.PATH_GENERAL)):

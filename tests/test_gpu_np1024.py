@@ -98,7 +98,7 @@ def test_np1024_fp16_scratch_vs_fp32_scratch():
 @pytest.mark.parametrize("fp16", [False, True], ids=["fp32", "fp16"])
 def test_objcrop_l4096_six_step_equals_batched_transform(fp16):
     """objCrop at L 4096 (config 5): the six-step column IDFT (64 x 64, two
-    passes of 128-byte row segments, objcrop.hip c4k) then the in-place row
+    passes of 128-byte row segments, crop4k.hip c4k) then the in-place row
     IDFT, vs the batched transform rows-then-columns (FPM_NO_CROP4K=1): the
     same 2-D IDFT in a different order, so within rounding (1e-6 relative L2)."""
     L, r = 4096, 333

@@ -2,9 +2,11 @@
 
 Every case of tests/objcrop_cases.py -- a context that reaches one of the six
 objCrop kernel families, a band the launchers accept -- through
-fpm_debug_objcrop: the product's launch_objcrop on a spectrum that is dense
-N(0,1) noise inside the band and NaN outside it, into an objCrop buffer filled
-with NaN.  The result must be finite everywhere (nothing outside the band was
+fpm_debug_objcrop: the product's launch_objcrop with the context's own plan
+on a spectrum that is dense N(0,1) noise inside the band and NaN outside it,
+into an objCrop buffer filled with NaN.  The plan read back from the context
+(fpm_debug_get_objcrop_plan) must name the family and the rows per block of
+the table row, so a context that stopped reaching its family fails.  The result must be finite everywhere (nothing outside the band was
 used, every element was written, no intermediate row was read that no pass
 wrote) and within BOUND = 2e-6 relative L2 of numpy's complex128 ifft2, per
 patch.  An fp32 CPU transform of the same inputs gives 1.2e-7 .. 2.3e-7
@@ -33,6 +35,9 @@ from tools.synth import grid_geometry, make_stack
 pytestmark = pytest.mark.gpu
 
 CASES = oc.cases()
+# fpm_objcrop_plan.kind of each family of the table
+KINDS = {oc.REGS: (fpm_amd.OBJCROP_REGS_256M, fpm_amd.OBJCROP_REGS_600, fpm_amd.OBJCROP_REGS_360),
+         oc.C4K: (fpm_amd.OBJCROP_SIX_STEP_4K,), oc.BATCHED: (fpm_amd.OBJCROP_BATCHED,)}
 
 
 @pytest.mark.parametrize("ctx,name", CASES, ids=[oc.case_id(c, b) for c, b in CASES])
@@ -42,7 +47,11 @@ def test_objcrop_case(ctx, name, monkeypatch):
     for k, v in ctx.env.items():
         monkeypatch.setenv(k, v)
     with fpm_amd.Solver(ctx.problem(name)) as s:
+        plan = s.debug_objcrop_plan()
         out = s.debug_objcrop(spec, oc.band(ctx, name))
+    # what the context launches is what the table row names (the switch was read at create)
+    assert plan["kind"] in KINDS[ctx.family] and plan["per_block"] == ctx.Gr, (ctx.id, plan)
+    assert plan == fpm_amd.debug_plan_objcrop(ctx.L, ctx.fp16, "FPM_NO_CROP4K" in ctx.env)
     assert out.shape == spec.shape and out.dtype == np.complex64
     bad = ~np.isfinite(out)
     assert not bad.any(), f"{np.count_nonzero(bad)} elements not finite, first at {tuple(np.argwhere(bad)[0])}"

@@ -2,7 +2,10 @@
 
 Band validity: every band of every context is one the launchers accept.
 Coverage: what the table says a band reaches is re-derived by arithmetic from
-   the kernels' launch geometry, restated here (objcrop.hip, fft_batch.hip).
+   the kernels' launch geometry, restated here (crop256m.hip, crop600.hip,
+   crop360.hip, crop4k.hip, fft_batch.hip), and the restatement is held against
+   the library's own planner (fpm_debug_plan_objcrop: plan_objcrop, no HIP call)
+   for every context of the table and over every L fpm_create accepts.
 Non-triviality: an fp32 CPU transform (torch complex64 ifft2) of every case's
    input stays below BOUND / 5 against the complex128 reference, so a GPU case
    that misses BOUND is wrong, not ill-conditioned.  The L 4096 contexts are
@@ -13,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+import fpm_amd
 import objcrop_cases as oc
 from fpm_oracle import rel_l2
 from objcrop_cases import BATCHED, BOUND, C4K, REGS
@@ -70,7 +74,7 @@ def batched_C(L):
 def rows_per_block(ctx):
     if ctx.family == BATCHED:
         return batched_C(ctx.L)
-    # launch_objcrop_regs: kCropGR 4; launch_crop600<2, 4, 2> / launch_crop360<1, 4>: 6 groups per wave, WR waves
+    # crop256m.hip kCropGR 4; crop600.hip WR 2 / crop360.hip WR 1: 6 groups per wave, WR waves; crop4k.hip CW 16
     return {512: 4, 768: 4, 1024: 4, 600: 6 * 2, 360: 6 * 1, 4096: 16}[ctx.L]
 
 
@@ -105,6 +109,79 @@ def test_rows_per_block_are_the_tables():
             pass
     assert (first[8, 0], first[8, 2], first[4, 2], first[1, 0]) == (720, 810, 1350, 5400)
     assert min(k[0] for k in first) == 1
+
+
+# ---- the restatement against the library's own planner ---------------------------------
+KINDS = {REGS: (fpm_amd.OBJCROP_REGS_256M, fpm_amd.OBJCROP_REGS_600, fpm_amd.OBJCROP_REGS_360),
+         C4K: (fpm_amd.OBJCROP_SIX_STEP_4K,), BATCHED: (fpm_amd.OBJCROP_BATCHED,)}
+LDS_LIMIT = 160 * 1024     # bytes of LDS a gfx950 workgroup can have
+
+
+def batched_lds(L):
+    """Tile of C padded sequences plus the twiddle table, complex64."""
+    return (batched_C(L) * (L + 1) + L) * 8
+
+
+@pytest.mark.parametrize("ctx", oc.CONTEXTS, ids=lambda c: c.id)
+def test_planner_names_the_tables_family(ctx):
+    """fpm_debug_plan_objcrop (plan_objcrop itself, no HIP call) for the
+    context's L, storage and switch: the row's family and rows per block."""
+    assert set(ctx.env) <= {"FPM_NO_CROP4K"}
+    plan = fpm_amd.debug_plan_objcrop(ctx.L, ctx.fp16, "FPM_NO_CROP4K" in ctx.env)
+    assert plan["kind"] in KINDS[ctx.family], (ctx.id, plan)
+    assert plan["per_block"] == ctx.Gr, (ctx.id, plan)
+    if ctx.family == REGS:
+        want = {600: fpm_amd.OBJCROP_REGS_600, 360: fpm_amd.OBJCROP_REGS_360}.get(ctx.L, fpm_amd.OBJCROP_REGS_256M)
+        assert plan["kind"] == want
+    if ctx.family == BATCHED:
+        assert plan["per_block"] == batched_C(ctx.L)
+
+
+def expected_kind(L, fp16, no_crop4k):
+    """The dispatch rule: register kinds only without fp16 storage, L 4096
+    six-step unless FPM_NO_CROP4K, everything else batched."""
+    if not fp16 and L in (512, 768, 1024):
+        return fpm_amd.OBJCROP_REGS_256M
+    if not fp16 and L == 600:
+        return fpm_amd.OBJCROP_REGS_600
+    if not fp16 and L == 360:
+        return fpm_amd.OBJCROP_REGS_360
+    if L == 4096 and not no_crop4k:
+        return fpm_amd.OBJCROP_SIX_STEP_4K
+    return fpm_amd.OBJCROP_BATCHED
+
+
+def test_planner_over_the_whole_domain():
+    """Every even 5-smooth L from 4 to 10240 (fft_max_len), fp32 and fp16
+    storage, with and without FPM_NO_CROP4K."""
+    sizes = []
+    for L in range(4, 10241, 2):
+        try:
+            radices(L)
+        except AssertionError:
+            continue
+        sizes.append(L)
+    assert {4, 360, 600, 768, 4096, 10000, 10240} <= set(sizes)
+    over = {}
+    for L in sizes:
+        for fp16 in (False, True):
+            for no_crop4k in (False, True):
+                plan = fpm_amd.debug_plan_objcrop(L, fp16, no_crop4k)
+                assert plan["kind"] == expected_kind(L, fp16, no_crop4k), (L, fp16, no_crop4k, plan)
+                if plan["kind"] == fpm_amd.OBJCROP_BATCHED:
+                    assert plan["per_block"] == batched_C(L)
+                    assert plan["rows_lds_dynamic"] == plan["cols_lds_dynamic"] == batched_lds(L), (L, plan)
+                    assert plan["rows_lds_static"] == plan["cols_lds_static"] == 0
+                for p in ("rows", "cols"):
+                    total = plan[p + "_lds_dynamic"] + plan[p + "_lds_static"]
+                    if total > LDS_LIMIT:
+                        over.setdefault(L, set()).add(total)
+    assert over == {10240: {163848}}, over
+    assert batched_lds(10000) == 160008 and batched_lds(10240) == 163848
+    for bad in (2, 7, 14, 10242, 10368):    # below 4, odd, not 5-smooth (10242 too), 5-smooth beyond the limit
+        with pytest.raises(fpm_amd.FpmError) as e:
+            fpm_amd.debug_plan_objcrop(bad)
+        assert e.value.code == fpm_amd.FPM_ERR_INVAL, bad
 
 
 # H mod C sequences of lo_hi / hi_lo lie before the first block boundary: 45 mod 16 = 13, 405 mod 8 = 5, 1215 mod 4 = 3
