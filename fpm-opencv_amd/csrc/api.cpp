@@ -98,6 +98,15 @@ int fpm_debug_get_plan(const fpm_ctx *c, int *meas_g, int *general_kind, int *re
     return FPM_OK;
 }
 
+int fpm_debug_get_band(const fpm_ctx *c, int band[4]) {
+    if (!c || !band) return set_err(FPM_ERR_INVAL, "null argument");
+    band[0] = c->st.sy0;
+    band[1] = c->st.sy1;
+    band[2] = c->st.sx0;
+    band[3] = c->st.sx1;
+    return FPM_OK;
+}
+
 int fpm_debug_get_maxima(const fpm_ctx *c, int *dims, float *tmax, unsigned char *dirty, float *rmax, float *pmax) {
     if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
     if (!c->initialized) return set_err(FPM_ERR_STATE, "fpm_debug_get_maxima before fpm_init");

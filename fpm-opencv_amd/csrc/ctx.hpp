@@ -5,6 +5,7 @@
 //   transfer.cpp  the stack uploads and the downloads
 //   run.cpp       fpm_init, fpm_run, the general path's patch groups and graphs
 //   residual_api.cpp  fpm_residual, fpm_residual_at, fpm_moments (kernels: residual.hip)
+//   state_api.cpp fpm_set_state, fpm_download_state_device (kernels: state.hip)
 //   api.cpp       errors, version, info, timing, clock, fpm_runFPM
 // Errors are negative codes plus fpm_last_error(); nothing here ever falls
 // back to a CPU path.
@@ -147,6 +148,8 @@ struct fpm_ctx {
     // fpm_moments' own: the per-block partials and the folded sums of C
     double *res_pcross = nullptr, *res_cross = nullptr;
     bool mom_ready = false;
+    // fpm_set_state's check scratch, allocated by its first call
+    fpm::StateCheck *state_chk = nullptr;
 
     fpm_ctx() = default;
     fpm_ctx(const fpm_ctx &) = delete;

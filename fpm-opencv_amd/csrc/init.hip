@@ -71,6 +71,11 @@ __global__ void __launch_bounds__(256) k_row_max_all(DevState st) {
     if (threadIdx.x == 0) st.rmax[(size_t)b * st.nty + ty] = m;
 }
 
+hipError_t launch_row_max_all(const DevState &st, hipStream_t s) {
+    hipLaunchKernelGGL(k_row_max_all, dim3(st.nty, st.B), dim3(256), 0, s, st);
+    return hipGetLastError();
+}
+
 hipError_t launch_init(const DevState &st, int init_led, float2 *scratch, const FftPlan &pl_np,
                        const float2 *tw_np, hipStream_t s) {
     const int np = st.np;

@@ -190,6 +190,28 @@ hipError_t launch_fft_batch(bool inverse, const float2 *in, float2 *out, const F
 // ---- fpm_init (init.hip)
 hipError_t launch_init(const DevState &st, int init_led, float2 *scratch, const FftPlan &pl_np,
                        const float2 *tw_np, hipStream_t s);
+// rmax from tmax (general path): k_row_max_all for a state that did not come from launch_init
+hipError_t launch_row_max_all(const DevState &st, hipStream_t s);
+
+// ---- fpm_set_state / fpm_download_state_device (state.hip)
+// Device scratch of the check pass: the lowest linear index, in the caller's
+// layout, of an offender in the spectrum ([0]) and in the pupil ([1]), ~0 =
+// none; behind it max|P S| of each patch, float [B].
+struct StateCheck {
+    unsigned long long first[2];
+};
+inline float *state_check_pmax(StateCheck *c) { return reinterpret_cast<float *>(c + 1); }
+inline size_t state_check_bytes(int B) { return sizeof(StateCheck) + (size_t)B * sizeof(float); }
+// objF [B][L][L] un-centred, pupil [B][Np][Np] (pupil_shared: [Np][Np]) centred,
+// both device memory, either null.  check writes chk only; place installs what
+// check accepted (the spectrum with its tile / row maxima and clean dirty
+// words, the pupil times the disk with chk's maxima as pmax); out is the
+// inverse copy.  fused: max|P| as the fused kernels round it.
+hipError_t launch_state_check(const DevState &st, const float2 *objF, const float2 *pupil, bool pupil_shared,
+                              bool fused, StateCheck *chk, hipStream_t s);
+hipError_t launch_state_place(const DevState &st, const float2 *objF, const float2 *pupil, bool pupil_shared,
+                              const StateCheck *chk, hipStream_t s);
+hipError_t launch_state_out(const DevState &st, float2 *objF, float2 *pupil, hipStream_t s);
 
 // ---- objCrop (objcrop.hip; kernels: crop256m.hip, crop600.hip, crop360.hip, crop4k.hip, fft_batch.hip)
 // The two launches of a register family, one table row per family file.  Every

@@ -88,6 +88,8 @@ int admit(fpm_ctx *c, const char *what, bool any_output) {
     if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
     if (!any_output) return set_err(FPM_ERR_INVAL, "%s: every output pointer is NULL", what);
     if (!c->initialized) return set_err(FPM_ERR_STATE, "%s before fpm_init", what);
+    // a state set by fpm_set_state on a context without a stack has no images to compare with
+    if (!c->uploaded) return set_err(FPM_ERR_STATE, "%s: no stack uploaded", what);
     HIP_TRY(hipSetDevice(c->device));
     return refuse_capture(c, what);
 }

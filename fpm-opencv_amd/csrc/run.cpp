@@ -218,6 +218,11 @@ int fpm_init(fpm_ctx *c) {
 int fpm_run(fpm_ctx *c, int iters) {
     if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
     if (!c->initialized) return set_err(FPM_ERR_STATE, "fpm_run before fpm_init");
+    // initialized used to imply uploaded (fpm_init was the only way in); fpm_set_state
+    // installs a state on a context without a stack, which has nothing to run on
+    if (!c->uploaded)
+        return set_err(FPM_ERR_STATE, "fpm_run: the state came from fpm_set_state and no stack is uploaded "
+                       "(fpm_upload_stack, then fpm_set_state again or fpm_init)");
     if (iters < 0) return set_err(FPM_ERR_INVAL, "iters=%d", iters);
     // a run that is refused or fails below reports zeros, not the previous run's values
     c->clock = fpm_clock{};

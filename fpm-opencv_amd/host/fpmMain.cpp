@@ -65,6 +65,19 @@
 //                      patch sums of Q - 2 g C + g^2 S at the old and the new
 //                      gains), moments_ms.  Combines with --calibrate-leds (the
 //                      positions first) and --residual
+//   --init-pupil FILE.npy  start from this pupil instead of the support disk:
+//                      complex64 [Np][Np] (one pupil for every patch) or
+//                      [patches][Np][Np], centred as pupil.npy / pupils.npy are
+//                      written; the library keeps it on the support disk only
+//   --init-objf FILE.npy   start from this spectrum: complex64 [Nlarge][Nlarge],
+//                      un-centred as objF.npy is written; single-patch runs only,
+//                      zero outside the band the used LEDs cover
+//                      Both apply after fpm_init (fpm_set_state); with both
+//                      given they apply instead of it, so objF.npy + pupil.npy
+//                      of a run resume it.  The files (little-endian '<c8', C
+//                      order, .npy version 1.0 or 2.0) are checked against the
+//                      dataset's Np / Nlarge / --grid before the GPU is touched.
+//                      result.json records what was used under "initial_state"
 //
 // Device selection: OPENCV_OPENCL_DEVICE (set by use_gpu.sh / use_cpu.sh) is
 // read with OpenCV's "<platform>:<type>:<device>" grammar and the scripts'
@@ -126,6 +139,85 @@ bool write_npy_c64_3d(const std::string &path, const float *data, int n0, int n1
     return fclose(f) == 0;
 }
 
+// A .npy file of little-endian complex64 in C order, format version 1.0 or
+// 2.0: its shape and its values as (re, im) pairs.  The header's shape must
+// be one of `accepted` (what the dataset allows; `layout` names them in the
+// message) before a value is read or a byte allocated for it.  Anything else
+// is an error whose text names the file.
+struct NpyC64 {
+    std::vector<int64_t> shape;
+    std::vector<float> data;
+};
+std::string shape_text(const std::vector<int64_t> &s) {
+    std::string t = "(";
+    for (size_t i = 0; i < s.size(); ++i) t += (i ? ", " : "") + std::to_string(s[i]);
+    return t + ")";
+}
+bool read_npy_c64(const std::string &path, const std::vector<std::vector<int64_t>> &accepted, const char *layout,
+                  NpyC64 *out, std::string *err) {
+    auto fail = [&](const std::string &why) {
+        *err = path + ": " + why;
+        return false;
+    };
+    std::ifstream f(path, std::ios::binary);
+    if (!f) return fail("cannot open");
+    unsigned char pre[12];
+    if (!f.read((char *)pre, 8) || std::memcmp(pre, "\x93NUMPY", 6) != 0) return fail("not a .npy file");
+    const int major = pre[6];
+    if (major != 1 && major != 2) return fail("unsupported .npy version " + std::to_string(major) + " (1.0 or 2.0)");
+    const int nlen = major == 1 ? 2 : 4;
+    if (!f.read((char *)pre + 8, nlen)) return fail("truncated header");
+    size_t hl = 0;
+    for (int i = 0; i < nlen; ++i) hl |= (size_t)pre[8 + i] << (8 * i);
+    if (hl > (1u << 20)) return fail("header too long");
+    std::string hdr(hl, '\0');
+    if (!f.read(&hdr[0], (std::streamsize)hl)) return fail("truncated header");
+    // the value that follows 'key': up to the next comma outside parentheses
+    auto value = [&](const char *key) {
+        size_t p = hdr.find(std::string("'") + key + "'");
+        if (p == std::string::npos) return std::string();
+        p = hdr.find(':', p);
+        if (p == std::string::npos) return std::string();
+        size_t q = ++p;
+        for (int depth = 0; q < hdr.size(); ++q) {
+            if (hdr[q] == '(') ++depth;
+            if (hdr[q] == ')') --depth;
+            if ((hdr[q] == ',' && depth == 0) || hdr[q] == '}') break;
+        }
+        std::string v = hdr.substr(p, q - p);
+        const size_t a = v.find_first_not_of(" "), b = v.find_last_not_of(" ");
+        return a == std::string::npos ? std::string() : v.substr(a, b - a + 1);
+    };
+    const std::string descr = value("descr"), forder = value("fortran_order"), shape = value("shape");
+    if (descr != "'<c8'" && descr != "\"<c8\"") return fail("dtype " + descr + ", want '<c8' (little-endian complex64)");
+    if (forder != "False") return fail("Fortran order, want C order");
+    if (shape.size() < 2 || shape.front() != '(' || shape.back() != ')') return fail("unreadable shape " + shape);
+    out->shape.clear();
+    for (size_t p = 1; p < shape.size() - 1;) {
+        const size_t q = std::min(shape.find(',', p), shape.size() - 1);
+        const std::string t = shape.substr(p, q - p);
+        if (t.find_first_not_of(" ") != std::string::npos) {
+            char *end = nullptr;
+            const long long v = strtoll(t.c_str(), &end, 10);
+            while (*end == ' ') ++end;
+            if (*end || v < 0 || v > (1ll << 31)) return fail("unreadable shape " + shape);
+            out->shape.push_back(v);
+        }
+        p = q + 1;
+    }
+    if (std::find(accepted.begin(), accepted.end(), out->shape) == accepted.end()) {
+        std::string want;
+        for (size_t i = 0; i < accepted.size(); ++i) want += (i ? " or " : "") + shape_text(accepted[i]);
+        return fail("shape " + shape_text(out->shape) + ", expected " + want + " (" + layout + ")");
+    }
+    size_t count = 1;  // of an accepted shape: the dataset's sizes
+    for (int64_t v : out->shape) count *= (size_t)v;
+    out->data.resize(count * 2);
+    if (!f.read((char *)out->data.data(), (std::streamsize)(count * 2 * sizeof(float))))
+        return fail("fewer values than its shape " + shape);
+    return true;
+}
+
 // OPENCV_OPENCL_DEVICE -> (refuse CPU, GPU ordinal).  OpenCV splits the value
 // at ':' into platform, device type(s) ('|'-separated) and device name/index;
 // use_gpu.sh / use_cpu.sh write "GPU:0" / "CPU:0" (type first).  Returns 3
@@ -179,7 +271,7 @@ int main(int argc, char **argv) {
         std::cout << "ERROR: Not enough input argumants.\n Usage: ./fpmMain dataset.json" << std::endl;
         return 0;
     }
-    std::string out_dir = ".", led_table, path_opt = "auto";
+    std::string out_dir = ".", led_table, path_opt = "auto", init_pupil, init_objf;
     int device = 0, device_opt = -1, gx = 0, gy = 0;
     bool want_residual = false;
     bool want_gains = false;  // --calibrate-gains: one gain step between the iterations
@@ -190,6 +282,8 @@ int main(int argc, char **argv) {
         else if (a == "--device" && i + 1 < argc) device_opt = atoi(argv[++i]);
         else if (a == "--led-table" && i + 1 < argc) led_table = argv[++i];
         else if (a == "--path" && i + 1 < argc) path_opt = argv[++i];
+        else if (a == "--init-pupil" && i + 1 < argc) init_pupil = argv[++i];
+        else if (a == "--init-objf" && i + 1 < argc) init_objf = argv[++i];
         else if (a == "--residual") want_residual = true;
         else if (a == "--calibrate-gains") want_gains = true;
         else if (a == "--calibrate-leds" && i + 1 < argc) {
@@ -233,6 +327,31 @@ int main(int argc, char **argv) {
     const int itr_count = atoi(argv[2]);  // fpmMain.cpp:569
     std::cout << "Dataset Root: " << cfg.dataset_root << std::endl;
     std::cout << "resImprovementFactor: " << cfg.res_improvement_factor << std::endl;
+    // --init-pupil / --init-objf: read and checked against the dataset before
+    // anything is loaded or the GPU is touched
+    NpyC64 pupil0, objf0;
+    bool pupil0_shared = false;
+    {
+        const int64_t n = cfg.np, l = cfg.nlarge, nb = gx > 0 ? gx * gy : 1;
+        std::string err;
+        if (!init_pupil.empty()) {
+            if (!read_npy_c64(init_pupil, {{n, n}, {nb, n, n}}, "[Np][Np] or [patches][Np][Np]", &pupil0, &err)) {
+                std::cerr << "--init-pupil " << err << std::endl;
+                return 2;
+            }
+            pupil0_shared = pupil0.shape.size() == 2;
+        }
+        if (!init_objf.empty()) {
+            if (nb != 1) {
+                std::cerr << "--init-objf " << init_objf << ": single-patch runs only (not with --grid)" << std::endl;
+                return 2;
+            }
+            if (!read_npy_c64(init_objf, {{l, l}}, "[Nlarge][Nlarge]", &objf0, &err)) {
+                std::cerr << "--init-objf " << err << std::endl;
+                return 2;
+            }
+        }
+    }
     if (!led_table.empty()) {
         std::vector<float> xyz;
         if (!read_led_table(led_table, &xyz)) {
@@ -339,7 +458,12 @@ int main(int argc, char **argv) {
         frames.clear();
         frames.shrink_to_fit();
     }
-    if (!rc) rc = fpm_init(ctx);
+    // a given pupil / spectrum replaces fpm_init's after it; both together replace it
+    const bool have_pupil0 = !init_pupil.empty(), have_objf0 = !init_objf.empty();
+    if (!rc && !(have_pupil0 && have_objf0)) rc = fpm_init(ctx);
+    if (!rc && (have_pupil0 || have_objf0))
+        rc = fpm_set_state(ctx, have_objf0 ? objf0.data.data() : nullptr, have_pupil0 ? pupil0.data.data() : nullptr,
+                           pupil0_shared ? FPM_STATE_PUPIL_SHARED : 0u);
     if (rc) {
         std::cerr << "fpm: " << fpm_last_error() << std::endl;
         return 1;
@@ -506,6 +630,24 @@ int main(int argc, char **argv) {
                     info.path == FPM_PATH_FUSED ? "fused" : "general", dt);
             for (int i = 0; i < used; ++i) fprintf(f, "%s%d", i ? ", " : "", order[i]);
             fprintf(f, "],\n");
+            if (have_pupil0 || have_objf0) {
+                // a path as a JSON string (quote, backslash and control characters escaped), or null
+                auto quoted = [](const std::string &s) {
+                    if (s.empty()) return std::string("null");
+                    std::string q = "\"";
+                    for (unsigned char ch : s) {
+                        char u[8];
+                        if (ch == '"' || ch == '\\') q += '\\', q += (char)ch;
+                        else if (ch < 0x20) snprintf(u, sizeof u, "\\u%04x", ch), q += u;
+                        else q += (char)ch;
+                    }
+                    return q + "\"";
+                };
+                fprintf(f, "  \"initial_state\": {\"pupil\": %s, \"pupil_shared\": %s, \"objf\": %s, "
+                           "\"replaces_init\": %s},\n",
+                        quoted(init_pupil).c_str(), have_pupil0 && pupil0_shared ? "true" : "false",
+                        quoted(init_objf).c_str(), have_pupil0 && have_objf0 ? "true" : "false");
+            }
             if (want_residual) {
                 fprintf(f, "  \"residual\": {\"per_iteration\": [");
                 for (size_t i = 0; i < res_iter_e.size(); ++i) put_ratio(f, i ? ", " : "", res_iter_e[i], res_iter_s[i]);

@@ -34,6 +34,9 @@ PATH_AUTO, PATH_GENERAL, PATH_FUSED = 0, 1, 2
 FLAG_OBJCROP_LAST_ONLY = 1
 FLAG_SPEC_FP16 = 2          # fp16 spectrum storage, fp32 arithmetic (config 5)
 FLAG_SCALAR_RE_ONLY = 4     # legacy: cv::add(UMat c2, double) on the real channel only (fpm_hip.h)
+# fpm_set_state flags (fpm_hip.h FPM_STATE_*)
+STATE_DEVICE = 1            # objF / pupil are device pointers on the context's device
+STATE_PUPIL_SHARED = 2      # one [Np][Np] pupil for every patch
 
 # fpm_info.fused_kernel: the LED-update kernel of the context (fpm_hip.h FPM_KERNEL_*)
 KERNEL_GENERAL, KERNEL_FUSED_NP256, KERNEL_FUSED_NP200, KERNEL_FUSED_SMALL, KERNEL_FUSED_NP256_DIST = 0, 1, 2, 3, 4
@@ -50,12 +53,12 @@ HIP_SYMBOLS = (
     "fpm_get_timing", "fpm_runFPM", "fpm_last_error", "fpm_version",
     "fpm_upload_frames", "fpm_download_stack", "fpm_get_info_sized", "fpm_abi_version",
     "fpm_get_clock", "fpm_residual", "fpm_residual_at", "fpm_set_crops", "fpm_get_crops",
-    "fpm_set_gains", "fpm_get_gains", "fpm_moments",
+    "fpm_set_gains", "fpm_get_gains", "fpm_moments", "fpm_set_state", "fpm_download_state_device",
 )
 # test-only entry points (include/fpm_hip_debug.h)
 HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan",
                      "fpm_debug_get_maxima", "fpm_debug_plan_ladder", "fpm_debug_get_ladder", "fpm_debug_objcrop",
-                     "fpm_debug_plan_objcrop", "fpm_debug_get_objcrop_plan")
+                     "fpm_debug_plan_objcrop", "fpm_debug_get_objcrop_plan", "fpm_debug_get_band")
 # fpm_ladder_kernel.generation
 LADDER_ONE_SEQ, LADDER_TILED, LADDER_WAVE = 0, 1, 2
 # fpm_objcrop_plan.kind
@@ -169,6 +172,7 @@ def load_library(path: str = HIP_LIB):
         "fpm_debug_set_stall": (C.c_int, [vp, C.c_int]),
         "fpm_debug_get_plan": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "fpm_debug_get_maxima": (C.c_int, [vp, C.POINTER(C.c_int), f32p, C.POINTER(C.c_uint8), f32p, f32p]),
+        "fpm_debug_get_band": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "fpm_debug_plan_ladder": (C.c_int, [C.c_int] * 6 + [C.POINTER(fpm_ladder)]),
         "fpm_debug_get_ladder": (C.c_int, [vp, C.c_int, C.POINTER(fpm_ladder)]),
         "fpm_debug_objcrop": (C.c_int, [vp, f32p, C.POINTER(C.c_int), f32p]),
@@ -184,6 +188,8 @@ def load_library(path: str = HIP_LIB):
         "fpm_set_gains": (C.c_int, [vp, f32p]),
         "fpm_get_gains": (C.c_int, [vp, f32p]),
         "fpm_moments": (C.c_int, [vp, C.POINTER(fpm_probe), C.c_int] + [C.POINTER(C.c_double)] * 4),
+        "fpm_set_state": (C.c_int, [vp, vp, vp, C.c_uint32]),
+        "fpm_download_state_device": (C.c_int, [vp, vp, vp]),
         "fpm_runFPM": (C.c_int, [C.POINTER(fpm_problem), C.c_int, u16p, C.c_int,
                                  f32p, f32p, f32p, f32p]),
         "fpm_upload_frames": (C.c_int, [vp, C.POINTER(fpm_frames), vp, C.c_int, C.POINTER(C.c_int16)]),
@@ -446,6 +452,55 @@ class Solver:
         _check(_lib.fpm_download(self._h, _f32p(oF), _f32p(oC), _f32p(pu), _f32p(su)))
         return dict(objF=oF, objCrop=oC, pupil=pu, support=su)
 
+    def _pairs(self, a, want, name):
+        """complex64, or float32 with a trailing axis of 2 (re, im), as a contiguous complex64 of shape `want`."""
+        a = np.asarray(a)
+        if a.dtype == np.float32 and a.ndim == len(want) + 1 and a.shape[-1] == 2:
+            a = np.ascontiguousarray(a).view(np.complex64)[..., 0]
+        elif a.dtype != np.complex64:
+            raise ValueError(f"{name}: dtype {a.dtype}, want complex64 or float32 (re, im) pairs")
+        if a.shape != want:
+            raise ValueError(f"{name} shape {a.shape} != {want}")
+        return np.ascontiguousarray(a)
+
+    def set_state(self, objF=None, pupil=None):
+        """fpm_set_state from host arrays in download()'s layouts: objF
+        [n_patch][L][L] un-centred ([L][L] if n_patch == 1), pupil
+        [n_patch][Np][Np] centred, or 2-D [Np][Np] = one pupil for every patch;
+        complex64 or float32 pairs.  None keeps what the context has (not
+        both).  With both given it replaces init().  Raises FpmError, the
+        context unchanged, when a value is not finite, the spectrum is nonzero
+        outside the live band or the pupil vanishes on the support."""
+        p = self.prob
+        flags = 0
+        if objF is not None:
+            o = np.asarray(objF)
+            if p.n_patch == 1 and o.ndim == (3 if o.dtype == np.float32 else 2):
+                o = o[None]
+            objF = self._pairs(o, (p.n_patch, p.L, p.L), "objF")
+        if pupil is not None:
+            q = np.asarray(pupil)
+            if q.ndim == (3 if q.dtype == np.float32 else 2):
+                flags |= STATE_PUPIL_SHARED
+                pupil = self._pairs(q, (p.np_, p.np_), "pupil")
+            else:
+                pupil = self._pairs(q, (p.n_patch, p.np_, p.np_), "pupil")
+        _check(_lib.fpm_set_state(self._h, None if objF is None else objF.ctypes.data_as(C.c_void_p),
+                                  None if pupil is None else pupil.ctypes.data_as(C.c_void_p), flags))
+
+    def set_state_device(self, objF_ptr: int | None, pupil_ptr: int | None, pupil_shared: bool = False):
+        """fpm_set_state from device memory on the context's device (float32
+        pairs in set_state's layouts); a pointer of None / 0 keeps what the
+        context has."""
+        _check(_lib.fpm_set_state(self._h, C.c_void_p(objF_ptr or 0), C.c_void_p(pupil_ptr or 0),
+                                  STATE_DEVICE | (STATE_PUPIL_SHARED if pupil_shared else 0)))
+
+    def download_state_device(self, objF_ptr: int | None, pupil_ptr: int | None):
+        """fpm_download_state_device: the un-centred fp32 spectrum
+        [n_patch][L][L][2] and the centred pupil [n_patch][Np][Np][2] into
+        device memory of the caller's; None / 0 skips one."""
+        _check(_lib.fpm_download_state_device(self._h, C.c_void_p(objF_ptr or 0), C.c_void_p(pupil_ptr or 0)))
+
     def download_objcrop_device(self, ptr: int):
         _check(_lib.fpm_download_objcrop_device(self._h, C.c_void_p(ptr)))
 
@@ -467,6 +522,14 @@ class Solver:
         g, k, r = C.c_int(), C.c_int(), C.c_int()
         _check(_lib.fpm_debug_get_plan(self._h, C.byref(g), C.byref(k), C.byref(r)))
         return dict(meas_g=g.value, general_kind=k.value, residual_kind=r.value)
+
+    def debug_band(self) -> tuple:
+        """Test-only (include/fpm_hip_debug.h): the live band (sy0, sy1, sx0, sx1),
+        inclusive, of the centred spectrum: set_state() refuses a spectrum that
+        is nonzero outside it."""
+        band = (C.c_int * 4)()
+        _check(_lib.fpm_debug_get_band(self._h, band))
+        return tuple(int(v) for v in band)
 
     def debug_maxima(self) -> dict:
         """Test-only (include/fpm_hip_debug.h): the carried max|objF| / max|P|

@@ -38,10 +38,12 @@ extern "C" {
  * revision.  Entry points appended since then change nothing a revision-6
  * caller sees, so the revision stands and each addition has a feature macro:
  * FPM_HAS_LED_CALIBRATION = fpm_residual_at, fpm_set_crops, fpm_get_crops;
- * FPM_HAS_LED_GAINS = fpm_set_gains, fpm_get_gains, fpm_moments. */
+ * FPM_HAS_LED_GAINS = fpm_set_gains, fpm_get_gains, fpm_moments;
+ * FPM_HAS_STATE = fpm_set_state, fpm_download_state_device. */
 #define FPM_ABI_VERSION   6
 #define FPM_HAS_LED_CALIBRATION 1
 #define FPM_HAS_LED_GAINS 1
+#define FPM_HAS_STATE 1
 
 #define FPM_OK            0
 #define FPM_ERR_INVAL   (-22)   /* bad argument / unsupported geometry      */
@@ -312,6 +314,52 @@ int  fpm_download(fpm_ctx *ctx, float *objF, float *objCrop, float *pupil,
 /* Device-to-device copy of objCrop [n_patch][L][L][2] into caller memory on
  * the context's device (for the multi-GPU gather). */
 int  fpm_download_objcrop_device(fpm_ctx *ctx, float *dst_dev);
+
+/* Install a solver state: warm start from a converged patch's pupil, resume
+ * from a checkpoint, or evaluate a hypothetical state with fpm_residual.
+ * Layouts are fpm_download's:
+ *   objF  [n_patch][L][L][2]    un-centred spectrum
+ *   pupil [n_patch][Np][Np][2]  centred pupil; FPM_STATE_PUPIL_SHARED: one
+ *                               [Np][Np][2] array used for every patch
+ * Host pointers, or with FPM_STATE_DEVICE both in device memory on the
+ * context's device (read in place).
+ * Call order.  Either pointer may be NULL = keep what the context has; not
+ * both.  With both given the call is legal on any created context (no stack
+ * uploaded, after a debug objCrop call, after a split-mode abort) and makes it
+ * initialised: it replaces fpm_init.  With one NULL the context must be
+ * initialised already, else FPM_ERR_STATE.  fpm_run, fpm_residual and their
+ * kin return FPM_ERR_STATE while no stack is uploaded; a later stack upload
+ * clears the state, as it always did.
+ * Pupil.  Stored is pupil * S, S the support disk: values outside the disk are
+ * ignored (the reference masks with pupilSupport, fpmMain.cpp:312,472).  Every
+ * value inside the disk must be finite, and max|P S| of every patch > 0
+ * (fpm_init's is 1; 0 would be 0/0 in the object update).
+ * Spectrum.  Every value finite; every element outside the context's live
+ * band (the rows and columns the support boxes of the init placement and of
+ * the used LEDs cover in the centred spectrum) exactly zero, anything inside
+ * it accepted; under FPM_FLAG_SPEC_FP16 |component| * hscale < 65504
+ * (hscale = 2^-ceil(log2 Np^2)).
+ * Any violation returns FPM_ERR_INVAL; the message names the array and the
+ * first offender in linear order as (patch, y, x) of the caller's layout.
+ * After a refused call the context is as it was: spectrum, pupil, maxima and
+ * the initialised flag bit for bit (objCrop may be recomputed lazily).
+ * Blocking; FPM_ERR_INVAL on a capturing stream before anything is enqueued.
+ * Gains, crops, the stack, fpm_timing and fpm_clock are untouched; objCrop is
+ * recomputed by the next fpm_download / fpm_run, as after fpm_init.  The
+ * carried maxima are rebuilt exactly from the stored values (under fp16
+ * storage: after its rounding), so a run resumed from a downloaded state
+ * continues as the run it came from.  The first call allocates a few bytes of
+ * check scratch (counted in fpm_info.device_bytes from then on). */
+#define FPM_STATE_DEVICE        1u  /* objF / pupil point to device memory on the context's device */
+#define FPM_STATE_PUPIL_SHARED  2u  /* pupil is one [Np][Np] array used for every patch */
+int  fpm_set_state(fpm_ctx *ctx, const float *objF, const float *pupil, uint32_t flags);
+
+/* The inverse: the un-centred fp32 spectrum [n_patch][L][L][2] (an fp16
+ * spectrum dequantised as fpm_download does) and the centred pupil
+ * [n_patch][Np][Np][2] into caller memory on the context's device.  Read-only
+ * and blocking.  Either pointer may be NULL, not both.  FPM_ERR_STATE before a
+ * state exists; FPM_ERR_INVAL on a capturing stream. */
+int  fpm_download_state_device(fpm_ctx *ctx, float *objF_dev, float *pupil_dev);
 
 /* Use a caller-provided hipStream_t (NULL = the context's own stream). */
 int  fpm_set_stream(fpm_ctx *ctx, void *hip_stream);

@@ -41,6 +41,12 @@ int fpm_debug_set_stall(fpm_ctx *ctx, int led);
  * context); residual_kind = fpm_residual's kernel pair (0 register, 1 LDS). */
 int fpm_debug_get_plan(const fpm_ctx *ctx, int *meas_g, int *general_kind, int *residual_kind);
 
+/* The live band of the centred spectrum the context planned (fpm_state.hpp),
+ * inclusive: band[4] = sy0, sy1, sx0, sx1.  Outside it the spectrum is exactly
+ * zero, and the state entry point of fpm_hip.h refuses a spectrum that is not;
+ * the crop-table entry point can grow it. */
+int fpm_debug_get_band(const fpm_ctx *ctx, int band[4]);
+
 /* The max|objF| / max|P| bookkeeping a context carries from one LED step and
  * one launch to the next (fpm_state.hpp), read back after synchronising the
  * context's stream; needs fpm_init.  Read-only: the device state is not
