@@ -4,6 +4,17 @@
 //
 // Layout: a 16-lane group holds 16 complex values per lane; a 256-point
 // transform is two register 16-point DFTs with one LDS exchange between them.
+//
+// The exchange comes in two forms.  exchange16 is the whole of it in one call,
+// sixteen row stores and eight reads back to back; objCrop, the general
+// path's register kernels, the residual sweep, the distributed kernel and the
+// KS 4 row transform use it, each with a schedule tuned around it (the
+// distributed kernel through fused256.hpp's transforms in their default
+// form).  exch_put / exch_get are its two parts, for those transforms as
+// fpm_fused.hip instantiates them: each store goes behind the twiddle block
+// that finishes its value, and the reads come in the order their consumer
+// needs them: 21.21 M -> 20.77 M kernel cycles per launch at the metric config
+// (DESIGN.md 4.1 "Exchange bursts").
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -107,6 +118,38 @@ __device__ __forceinline__ void exchange16(float2 *scr, int t, int xrd, const fl
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float4 q = rp[j];
+        z[2 * j] = make_float2(q.x, q.y);
+        z[2 * j + 1] = make_float2(q.z, q.w);
+    }
+}
+
+// The exchange in two parts, for the transforms of the Np 256 fused kernel
+// (fused256.hpp): the same tile, the same laundered read base, so every get
+// stays behind every put of its exchange and every put of the next exchange
+// behind these gets.
+//   exch_put  one row store; the caller places it behind the twiddle block
+//             that finishes y[m1] instead of after all fifteen, so the DS
+//             queue takes the stores while the VALU still has twiddles to do
+//   exch_get  the eight 16-byte reads in the order the stage that follows
+//             consumes them.  Its first radix-4 butterflies pair z[k1],
+//             z[k1 + 4], z[k1 + 8], z[k1 + 12] (the pbf4 loop of pdft16 /
+//             pdft16_out6, cpk.hpp; pdft16_inhalf_out6 pairs z[8 j + k1],
+//             z[8 j + k1 + 4]) and read j holds z[2 j], z[2 j + 1], so reads
+//             0, 2, 4, 6 go first, then 1, 3, 5, 7: butterflies k1 = 0, 1 have
+//             their operands after four reads and run while the other four
+//             land (reads return in issue order).  The odd reads go through a
+//             base register of their own: the compiler sorts the loads of one
+//             base by offset, whatever the program order.
+__device__ __forceinline__ void exch_put(float2 *scr, int t, int m1, float2 y) { scr[m1 * XP + t] = y; }
+__device__ __forceinline__ void exch_get(const float2 *scr, int xrd, float2 (&z)[16]) {
+    const float4 *rp = (const float4 *)(scr + xrd);  // 16-B aligned: XTILE and XP even
+    int xodd = xrd + 2;
+    asm("" : "+v"(xodd));
+    const float4 *ro = (const float4 *)(scr + xodd);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int j = 2 * (i & 3) + (i >> 2);
+        const float4 q = (j & 1) ? ro[j - 1] : rp[j];
         z[2 * j] = make_float2(q.x, q.y);
         z[2 * j + 1] = make_float2(q.z, q.w);
     }

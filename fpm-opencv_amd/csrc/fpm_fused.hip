@@ -393,7 +393,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
                     for (int k = 0; k < 16; ++k) v[k] = make_float2(0.f, 0.f);
 #pragma unroll
                     for (int s = 0; s < 6; ++s) v[SK[s]] = X[j][s];
-                    idft256_in6(v, r, scr, wt, t, xrd);
+                    idft256_in6<kXSpread>(v, r, scr, wt, t, xrd);
                     // keep the column part h: row[16 m'] = r[h MPP + m'] (one branch
                     // per part keeps every register index static; a shared helper
                     // made the compiler select between addresses of r and put r
@@ -470,7 +470,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
                 for (int k = 0; k < 16; ++k) v[k] = make_float2(0.f, 0.f);
 #pragma unroll
                 for (int s = 0; s < 6; ++s) v[SK[s]] = tin[s];
-                idft256_in6(v, r, scr, wt, t, xrd);
+                idft256_in6<kXSpread>(v, r, scr, wt, t, xrd);
                 {
                     // next block's T slots; unconditional (the last round
                     // re-reads its own column) so the loads are not sunk into
@@ -492,7 +492,7 @@ __global__ void __launch_bounds__(NT, 1) k_fused_iteration(FusedArgs a) {
                     v[m2] = pout(pin(r[m2]) * sc);
                 }
                 float2 o[6];
-                dft256_out6(v, o, scr, wt, t, xrd);
+                dft256_out6<kXSpread>(v, o, scr, wt, t, xrd);
 #pragma unroll
                 for (int s = 0; s < 6; ++s) th[roff[s] + (roff[s] == zoff ? TLD : 0) + xl] = o[s];
                 if (nx >= NBLK) break;

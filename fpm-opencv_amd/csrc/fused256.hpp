@@ -114,34 +114,87 @@ struct Tw {
     __device__ __forceinline__ float2 operator[](int m) const { return w[m]; }
 };
 
+// ---------------------------------------------- the exchange, spread out
+// exchange16 (dft16.hpp) issues its sixteen row stores and eight reads as one
+// burst behind the last twiddle: the wave queues behind its own burst at LDS
+// issue and then sits through the round trip.  fpm_fused.hip asks the
+// transforms below for the spread form instead (template flag SPREAD, the
+// pair transforms always): the exchange in its two parts (exch_put /
+// exch_get, dft16.hpp), every row store right behind the twiddle block that
+// finishes it (twiddle_put) and the reads in the order their consumer's first
+// butterflies need them.  The flag defaults to the exchange16 form, which the
+// distributed kernel (fused_dist.hip) keeps: its schedule was tuned around
+// that form and the spread one has not been measured there.  The values and
+// the tile slots are the same in both forms, so results do not depend on it.
+// FPM_XSPREAD=0 builds fpm_fused.hip on the exchange16 form too, for same-box
+// A/B runs.  Measured: DESIGN.md 4.1 "Exchange bursts".
+#ifndef FPM_XSPREAD
+#define FPM_XSPREAD 1
+#endif
+constexpr bool kXSpread = FPM_XSPREAD != 0;  // what fpm_fused.hip passes as SPREAD
+
+// py[m] *= w[m] (CONJ: by conj(w[m])) for m in [M0, M1) in blocks split the
+// way ptw_range (cpk.hpp) splits them, every block's rows stored to tile row
+// row0 + m right behind it
+template <bool CONJ, int M0, int M1>
+__device__ __forceinline__ void twiddle_put(pf2 *py, const pf2 *w, float2 *scr, int t, int row0 = 0) {
+    constexpr int n = M1 - M0, nb = (n + 4) / 5;
+    static_assert(n >= 3, "every block holds 3..5 twiddles (ptw_block)");
+#pragma unroll
+    for (int b = 0, i = M0; b < nb; ++b) {
+        const int len = (n - (i - M0)) / (nb - b);  // 3..5 for n >= 3
+        if (len == 5) ptw_block<CONJ, 5>(&py[i], &w[i]);
+        else if (len == 4) ptw_block<CONJ, 4>(&py[i], &w[i]);
+        else ptw_block<CONJ, 3>(&py[i], &w[i]);
+#pragma unroll
+        for (int m = i; m < i + len; ++m) exch_put(scr, t, row0 + m, pout(py[m]));
+        i += len;
+    }
+}
+
+// the four-step exchange behind a transform's fifteen twiddles: y[m] = py[m]
+// wt[m] (CONJ: conj) through the tile, z[j] = y_of_lane_j[t] out
+template <bool CONJ, bool SPREAD, class TW>
+__device__ __forceinline__ void twiddle_exchange(pf2 (&py)[16], const TW &wt, float2 *scr, int t, int xrd,
+                                                 float2 (&z)[16]) {
+    if constexpr (SPREAD) {
+        pf2 w[16];
+#pragma unroll
+        for (int m = 1; m < 16; ++m) w[m] = pin(wt[m]);
+        w[0] = w[1];
+        exch_put(scr, t, 0, pout(py[0]));  // no twiddle
+        twiddle_put<CONJ, 1, 16>(py, w, scr, t);
+        exch_get(scr, xrd, z);
+    } else {
+        ptwiddle15<CONJ>(py, wt);
+        float2 y[16];
+        from_pk(py, y);
+        exchange16(scr, t, xrd, y, z);
+    }
+}
+
 // inverse 256-point DFT (unscaled), input v[k] = X[t + 16 k] (only the six
 // SK registers may be non-zero), output r[m2] = x[t + 16 m2]
-template <class TW>
+template <bool SPREAD = false, class TW>
 __device__ __forceinline__ void idft256_in6(float2 (&v)[16], float2 (&r)[16], float2 *scr, const TW &wt, int t,
                                             int xrd) {
     pf2 pv[16], py[16];
     to_pk(v, pv);
     pdft16_in6<true>(pv, py);
-    ptwiddle15<true>(py, wt);
-    float2 y[16];
-    from_pk(py, y);
-    exchange16(scr, t, xrd, y, v);
+    twiddle_exchange<true, SPREAD>(py, wt, scr, t, xrd, v);
     to_pk(v, pv);
     pdft16<true>(pv, py);
     from_pk(py, r);
 }
 
 // forward 256-point DFT, input v[n2] = x[t + 16 n2], output o[s] = X[t + 16 SK[s]]
-template <class TW>
+template <bool SPREAD = false, class TW>
 __device__ __forceinline__ void dft256_out6(float2 (&v)[16], float2 (&o)[6], float2 *scr, const TW &wt, int t,
                                             int xrd) {
     pf2 pv[16], py[16], po[6];
     to_pk(v, pv);
     pdft16<false>(pv, py);
-    ptwiddle15<false>(py, wt);
-    float2 y[16];
-    from_pk(py, y);
-    exchange16(scr, t, xrd, y, v);
+    twiddle_exchange<false, SPREAD>(py, wt, scr, t, xrd, v);
     to_pk(v, pv);
     pdft16_out6<false>(pv, po);
     from_pk(po, o);
@@ -300,6 +353,28 @@ __device__ __forceinline__ void idft256_pair_stage1(const float2 (&X)[2][6], pf2
         }
     }
 }
+// the same with every twiddle block's rows stored to the exchange tile right
+// behind it (twiddle_put; the same blocks as above), one row after the other
+template <int H, class TW>
+__device__ __forceinline__ void idft256_pair_stage1_put(const float2 (&X)[2][6], const TW &wt, float2 *scr, int t) {
+    pf2 w[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) w[i] = pin(wt[8 * H + i]);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        pf2 in[6], o[8];
+        to_pk(X[j], in);
+        pdft16_in6_outhalf<true, H>(in, o);
+        if constexpr (H == 0) {
+            exch_put(scr, t, 8 * j, pout(o[0]));  // x1 = 0: no twiddle
+            twiddle_put<true, 1, 5>(o, w, scr, t, 8 * j);
+            twiddle_put<true, 5, 8>(o, w, scr, t, 8 * j);
+        } else {
+            twiddle_put<true, 0, 4>(o, w, scr, t, 8 * j);
+            twiddle_put<true, 4, 8>(o, w, scr, t, 8 * j);
+        }
+    }
+}
 
 // inverse 256-point DFTs (unscaled) of the two rows of a group, column half h
 // (block-uniform): input X[j][s] = X_j[t + 16 SK[s]], output r[x2] =
@@ -309,11 +384,17 @@ template <class TW>
 __device__ __forceinline__ void idft256_pair_in6(const float2 (&X)[2][6], float2 (&v)[16], float2 (&r)[16], float2 *scr,
                                                  const TW &wt, int t, int xrd, int h) {
     pf2 pv[16], py[16];
-    if (h == 0) idft256_pair_stage1<0>(X, py, wt);
-    else idft256_pair_stage1<1>(X, py, wt);
-    float2 y[16];
-    from_pk(py, y);
-    exchange16(scr, t, xrd, y, v);
+    if constexpr (kXSpread) {
+        if (h == 0) idft256_pair_stage1_put<0>(X, wt, scr, t);
+        else idft256_pair_stage1_put<1>(X, wt, scr, t);
+        exch_get(scr, xrd, v);
+    } else {
+        if (h == 0) idft256_pair_stage1<0>(X, py, wt);
+        else idft256_pair_stage1<1>(X, py, wt);
+        float2 y[16];
+        from_pk(py, y);
+        exchange16(scr, t, xrd, y, v);
+    }
     to_pk(v, pv);
     pdft16<true>(pv, py);
     from_pk(py, r);
@@ -329,10 +410,7 @@ __device__ __forceinline__ void dft256_pair_out6(float2 (&v)[16], float2 (&o)[2]
     pf2 pv[16], py[16];
     to_pk(v, pv);
     pdft16<false>(pv, py);
-    ptwiddle15<false>(py, wx);
-    float2 y[16];
-    from_pk(py, y);
-    exchange16(scr, t, xrd, y, v);
+    twiddle_exchange<false, kXSpread>(py, wx, scr, t, xrd, v);
     to_pk(v, pv);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
