@@ -6,6 +6,7 @@
 //   run.cpp       fpm_init, fpm_run, the general path's patch groups and graphs
 //   residual_api.cpp  fpm_residual, fpm_residual_at, fpm_moments (kernels: residual.hip)
 //   state_api.cpp fpm_set_state, fpm_download_state_device (kernels: state.hip)
+//   stitch_api.cpp fpm_stitch_tiles, fpm_stitch (kernels: stitch.hip; solve: stitch_solve.hpp)
 //   api.cpp       errors, version, info, timing, clock, fpm_runFPM
 // Errors are negative codes plus fpm_last_error(); nothing here ever falls
 // back to a CPU path.

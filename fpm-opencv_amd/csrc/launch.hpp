@@ -213,6 +213,27 @@ hipError_t launch_state_place(const DevState &st, const float2 *objF, const floa
                               const StateCheck *chk, hipStream_t s);
 hipError_t launch_state_out(const DevState &st, float2 *objF, float2 *pupil, hipStream_t s);
 
+// ---- fpm_stitch / fpm_stitch_tiles (stitch.hip)
+// gy x gx tiles of L x L at strides (sy, sx) and the H x W field they cover
+struct StitchGeom {
+    int gy, gx, L, sy, sx, H, W;
+};
+// Workgroups per neighbour pair of the pair-sum pass: what a left/right and an
+// up/down region need, and the larger of the two (>= 1), the pitch of partials
+struct StitchParts {
+    int lr, ud, parts;
+};
+StitchParts stitch_pair_parts(const StitchGeom &g);
+// (c_re, c_im, a, b) of every neighbour pair (stitch_solve.hpp: StitchPairSums,
+// pair order) into sums [pairs][4]; partials [pairs][parts][4] is scratch
+hipError_t launch_stitch_pairs(const StitchGeom &g, const float2 *tiles, double *partials, double *sums,
+                               hipStream_t s);
+// field [H][W] = sum_t w_t factors[t] T[t]; factors [gy*gx] or null = all ones.
+// stitch_blend_vector: the launch takes the 16-byte path
+bool stitch_blend_vector(const StitchGeom &g, const float2 *tiles, const float2 *field);
+hipError_t launch_stitch_blend(const StitchGeom &g, const float2 *tiles, const float2 *factors, float2 *field,
+                               hipStream_t s);
+
 // ---- objCrop (objcrop.hip; kernels: crop256m.hip, crop600.hip, crop360.hip, crop4k.hip, fft_batch.hip)
 // The two launches of a register family, one table row per family file.  Every
 // row kernel takes (spec, out, tw, sy0, sy1, sx0, sx1) and every column kernel

@@ -27,6 +27,19 @@
 //                      (GY*Nlarge x GX*Nlarge complex64) is written as
 //                      objCrop_field.npy with pupils.npy [B][Np][Np] (SURVEY.md
 //                      8(f2)); result.json describes the grid
+//   --overlap V        with --grid: neighbouring patches share V low-resolution
+//                      pixels (0 <= V <= Np/2): patch (i, j) is cut at
+//                      (cropX + j*(Np-V), cropY + i*(Np-V)), and the field is the
+//                      tiles aligned and feathered on the GPU (fpm_stitch) at the
+//                      stride (Np-V)*resImprovementFactor:
+//                      ((GY-1)*stride + Nlarge) x ((GX-1)*stride + Nlarge).
+//                      result.json gains "stitch": overlap, stride, align, field
+//                      [H, W], factors [patches][2] (re, im), stitch_ms
+//   --stitch-align none|phase|complex   with --overlap: bring every patch to its
+//                      left and upper neighbours' phase (and, complex, scale) over
+//                      the pixels they share before blending; default phase when
+//                      V > 0
+//   --write-tiles      also write objCrop_tiles.npy [patches][Nlarge][Nlarge]
 //   --residual         report how well the state fits the data: fpm_residual
 //                      after fpm_init and after every iteration (the iterations
 //                      already run one fpm_run(ctx, 1) at a time, and a split run
@@ -276,9 +289,29 @@ int main(int argc, char **argv) {
     bool want_residual = false;
     bool want_gains = false;  // --calibrate-gains: one gain step between the iterations
     int cal_radius = -1;  // --calibrate-leds R: a window search of radius R between the iterations
+    int overlap = -1;          // --overlap V: low-resolution pixels neighbouring patches share (-1: not given)
+    std::string stitch_align;  // --stitch-align none|phase|complex
+    bool write_tiles = false;  // --write-tiles: objCrop_tiles.npy [B][L][L] as well
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--out" && i + 1 < argc) out_dir = argv[++i];
+        else if (a == "--write-tiles") write_tiles = true;
+        else if (a == "--overlap" && i + 1 < argc) {
+            char *end = nullptr;
+            const long v = strtol(argv[++i], &end, 10);
+            if (end == argv[i] || *end || v < 0 || v > (1 << 20)) {
+                std::cerr << "--overlap wants a number of pixels >= 0" << std::endl;
+                return 2;
+            }
+            overlap = (int)v;
+        }
+        else if (a == "--stitch-align" && i + 1 < argc) {
+            stitch_align = argv[++i];
+            if (stitch_align != "none" && stitch_align != "phase" && stitch_align != "complex") {
+                std::cerr << "--stitch-align wants none, phase or complex" << std::endl;
+                return 2;
+            }
+        }
         else if (a == "--device" && i + 1 < argc) device_opt = atoi(argv[++i]);
         else if (a == "--led-table" && i + 1 < argc) led_table = argv[++i];
         else if (a == "--path" && i + 1 < argc) path_opt = argv[++i];
@@ -302,6 +335,14 @@ int main(int argc, char **argv) {
             std::cerr << "unknown option " << a << std::endl;
             return 2;
         }
+    }
+    if (overlap >= 0 && gx < 1) {
+        std::cerr << "--overlap needs --grid: it is the overlap of the grid's neighbouring patches" << std::endl;
+        return 2;
+    }
+    if (!stitch_align.empty() && overlap < 0) {
+        std::cerr << "--stitch-align needs --overlap: without it the tiles share no pixels to align on" << std::endl;
+        return 2;
     }
     // use_cpu.sh / use_gpu.sh select the OpenCL device (use_gpu.sh:1)
     const char *dev = getenv("OPENCV_OPENCL_DEVICE");
@@ -327,6 +368,13 @@ int main(int argc, char **argv) {
     const int itr_count = atoi(argv[2]);  // fpmMain.cpp:569
     std::cout << "Dataset Root: " << cfg.dataset_root << std::endl;
     std::cout << "resImprovementFactor: " << cfg.res_improvement_factor << std::endl;
+    if (overlap > cfg.np / 2) {
+        std::cerr << "--overlap " << overlap << " exceeds Np/2 = " << cfg.np / 2
+                  << ": a pixel may lie in at most two patches per axis" << std::endl;
+        return 2;
+    }
+    if (overlap > 0 && stitch_align.empty()) stitch_align = "phase";
+    if (overlap == 0 && stitch_align.empty()) stitch_align = "none";
     // --init-pupil / --init-objf: read and checked against the dataset before
     // anything is loaded or the GPU is touched
     NpyC64 pupil0, objf0;
@@ -427,13 +475,15 @@ int main(int argc, char **argv) {
     std::vector<int16_t> bg(used, 0);
     if (!rc && !grid) rc = fpm_upload_stack(ctx, stack.data());
     if (!rc && grid) {
-        // patch (i, j) of the field at (cropX + j Np, cropY + i Np); the
-        // darkfield divide applies where illumination NA > objective NA (:128)
+        // patch (i, j) of the field at (cropX + j step, cropY + i step), step = Np
+        // less --overlap; the darkfield divide applies where illumination NA >
+        // objective NA (:128)
+        const int step = np - std::max(overlap, 0);
         std::vector<int32_t> px(B), py(B);
         for (int i = 0; i < gy; ++i)
             for (int j = 0; j < gx; ++j) {
-                px[i * gx + j] = cfg.crop_x + j * np;
-                py[i * gx + j] = cfg.crop_y + i * np;
+                px[i * gx + j] = cfg.crop_x + j * step;
+                py[i * gx + j] = cfg.crop_y + i * step;
             }
         std::vector<fpm_host_led> all(fpm_host_n_present(h));
         fpm_host_get_leds(h, all.data(), (int)all.size());
@@ -595,6 +645,25 @@ int main(int argc, char **argv) {
         std::cerr << "fpm: " << fpm_last_error() << std::endl;
         return 1;
     }
+    // --overlap: the field is the tiles aligned and blended on the GPU (fpm_stitch)
+    const bool blend = grid && overlap >= 0;
+    const int st_stride = (np - std::max(overlap, 0)) * (L / np);  // Nlarge = Np * resImprovementFactor
+    const int st_h = (gy - 1) * st_stride + L, st_w = (gx - 1) * st_stride + L;
+    std::vector<float> st_field;
+    std::vector<double> st_factors;
+    double st_ms = 0;
+    if (blend) {
+        st_field.resize((size_t)st_h * st_w * 2);
+        st_factors.resize((size_t)B * 2);
+        const fpm_stitch_grid sg = {gy, gx, L, st_stride, st_stride};
+        const uint32_t sflags = stitch_align == "phase"     ? FPM_STITCH_ALIGN_PHASE
+                                : stitch_align == "complex" ? FPM_STITCH_ALIGN_COMPLEX
+                                                            : 0u;
+        if ((rc = fpm_stitch(ctx, &sg, sflags, st_field.data(), st_factors.data(), &st_ms))) {
+            std::cerr << "fpm: " << fpm_last_error() << std::endl;
+            return 1;
+        }
+    }
     fpm_info info;
     fpm_get_info_sized(ctx, &info, sizeof info);
     fpm_destroy(ctx);
@@ -604,6 +673,9 @@ int main(int argc, char **argv) {
         ok = write_npy_c64(out_dir + "/objCrop.npy", objCrop.data(), L, L) &&
              write_npy_c64(out_dir + "/objF.npy", objF.data(), L, L) &&
              write_npy_c64(out_dir + "/pupil.npy", pupil.data(), np, np);
+    } else if (blend) {
+        ok = write_npy_c64(out_dir + "/objCrop_field.npy", st_field.data(), st_h, st_w) &&
+             write_npy_c64_3d(out_dir + "/pupils.npy", pupil.data(), B, np, np);
     } else {
         // stitch: tile b = (i, j) lands at rows i L, columns j L (tiles do not
         // overlap); row-wise copies of L complex values
@@ -618,6 +690,7 @@ int main(int argc, char **argv) {
         ok = write_npy_c64(out_dir + "/objCrop_field.npy", field.data(), gy * L, gx * L) &&
              write_npy_c64_3d(out_dir + "/pupils.npy", pupil.data(), B, np, np);
     }
+    if (ok && write_tiles) ok = write_npy_c64_3d(out_dir + "/objCrop_tiles.npy", objCrop.data(), B, L, L);
     if (ok) {  // JSON sidecar describing the arrays (replaces the reference's display windows)
         FILE *f = fopen((out_dir + "/result.json").c_str(), "w");
         ok = f != nullptr;
@@ -702,19 +775,37 @@ int main(int argc, char **argv) {
                 }
                 fprintf(f, "], \"moments_ms\": %.6f},\n", gain_ms);
             }
+            if (blend) {  // factors in row-major patch order, (re, im)
+                fprintf(f, "  \"stitch\": {\"overlap\": %d, \"stride\": %d, \"align\": \"%s\", \"field\": [%d, %d], "
+                           "\"factors\": [", overlap, st_stride, stitch_align.c_str(), st_h, st_w);
+                for (int b = 0; b < B; ++b)
+                    fprintf(f, "%s[%.17g, %.17g]", b ? ", " : "", st_factors[2 * b], st_factors[2 * b + 1]);
+                fprintf(f, "], \"stitch_ms\": %.6f},\n", st_ms);
+            }
             if (grid) {
                 fprintf(f, "  \"grid\": {\"gx\": %d, \"gy\": %d, \"patches\": %d, \"frame\": [%d, %d], "
                            "\"patch_origin\": [%d, %d], \"patch_step\": %d},\n  \"bg_val\": [",
-                        gx, gy, B, fh, fw, cfg.crop_x, cfg.crop_y, np);
+                        gx, gy, B, fh, fw, cfg.crop_x, cfg.crop_y, np - std::max(overlap, 0));
                 for (int i = 0; i < used; ++i) fprintf(f, "%s%d", i ? ", " : "", bg[i]);
                 fprintf(f, "],\n  \"arrays\": {\n");
-                fprintf(f, "    \"objCrop_field.npy\": \"complex64 [gy*Nlarge][gx*Nlarge], patch (i, j) = "
-                           "IDFT(objF)/Nlarge^2 of the crop at (cropX + j*Np, cropY + i*Np) at rows i*Nlarge, "
-                           "columns j*Nlarge\",\n");
+                if (write_tiles)
+                    fprintf(f, "    \"objCrop_tiles.npy\": \"complex64 [gy*gx][Nlarge][Nlarge], IDFT(objF)/Nlarge^2 per "
+                               "patch, row-major patch order\",\n");
+                if (blend)
+                    fprintf(f, "    \"objCrop_field.npy\": \"complex64 [(gy-1)*stride+Nlarge][(gx-1)*stride+Nlarge], "
+                               "the patches' objCrop tiles at rows i*stride, columns j*stride times their stitch "
+                               "factors, feathered over the overlaps (fpm_stitch)\",\n");
+                else
+                    fprintf(f, "    \"objCrop_field.npy\": \"complex64 [gy*Nlarge][gx*Nlarge], patch (i, j) = "
+                               "IDFT(objF)/Nlarge^2 of the crop at (cropX + j*Np, cropY + i*Np) at rows i*Nlarge, "
+                               "columns j*Nlarge\",\n");
                 fprintf(f, "    \"pupils.npy\": \"complex64 [gy*gx][Np][Np], centred pupil per patch, row-major "
                            "patch order\"\n  }\n}\n");
             } else {
                 fprintf(f, "  \"arrays\": {\n");
+                if (write_tiles)
+                    fprintf(f, "    \"objCrop_tiles.npy\": \"complex64 [1][Nlarge][Nlarge], objCrop.npy as the one tile of "
+                               "a single-patch run\",\n");
                 fprintf(f, "    \"objCrop.npy\": \"complex64 [Nlarge][Nlarge], IDFT(objF)/Nlarge^2 (fpmMain.cpp:481)\",\n");
                 fprintf(f, "    \"objF.npy\": \"complex64 [Nlarge][Nlarge], un-centred object spectrum\",\n");
                 fprintf(f, "    \"pupil.npy\": \"complex64 [Np][Np], centred pupil (fpmMain.cpp:496)\"\n  }\n}\n");

@@ -37,6 +37,11 @@ FLAG_SCALAR_RE_ONLY = 4     # legacy: cv::add(UMat c2, double) on the real chann
 # fpm_set_state flags (fpm_hip.h FPM_STATE_*)
 STATE_DEVICE = 1            # objF / pupil are device pointers on the context's device
 STATE_PUPIL_SHARED = 2      # one [Np][Np] pupil for every patch
+# fpm_stitch / fpm_stitch_tiles flags (fpm_hip.h FPM_STITCH_*)
+STITCH_ALIGN_PHASE = 1      # neighbours brought to a common phase
+STITCH_ALIGN_COMPLEX = 2    # phase and scale
+STITCH_DEVICE = 4           # tiles / field are device pointers
+STITCH_ALIGN = {"none": 0, "phase": STITCH_ALIGN_PHASE, "complex": STITCH_ALIGN_COMPLEX}
 
 # fpm_info.fused_kernel: the LED-update kernel of the context (fpm_hip.h FPM_KERNEL_*)
 KERNEL_GENERAL, KERNEL_FUSED_NP256, KERNEL_FUSED_NP200, KERNEL_FUSED_SMALL, KERNEL_FUSED_NP256_DIST = 0, 1, 2, 3, 4
@@ -54,6 +59,7 @@ HIP_SYMBOLS = (
     "fpm_upload_frames", "fpm_download_stack", "fpm_get_info_sized", "fpm_abi_version",
     "fpm_get_clock", "fpm_residual", "fpm_residual_at", "fpm_set_crops", "fpm_get_crops",
     "fpm_set_gains", "fpm_get_gains", "fpm_moments", "fpm_set_state", "fpm_download_state_device",
+    "fpm_stitch_tiles", "fpm_stitch",
 )
 # test-only entry points (include/fpm_hip_debug.h)
 HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan",
@@ -115,6 +121,11 @@ class fpm_clock(C.Structure):
 
 class fpm_probe(C.Structure):
     _fields_ = [("pos", C.c_int32), ("dx", C.c_int32), ("dy", C.c_int32)]
+
+
+class fpm_stitch_grid(C.Structure):
+    _fields_ = [("gy", C.c_int32), ("gx", C.c_int32), ("tile", C.c_int32),
+                ("stride_y", C.c_int32), ("stride_x", C.c_int32)]
 
 
 class fpm_ladder_kernel(C.Structure):
@@ -190,6 +201,10 @@ def load_library(path: str = HIP_LIB):
         "fpm_moments": (C.c_int, [vp, C.POINTER(fpm_probe), C.c_int] + [C.POINTER(C.c_double)] * 4),
         "fpm_set_state": (C.c_int, [vp, vp, vp, C.c_uint32]),
         "fpm_download_state_device": (C.c_int, [vp, vp, vp]),
+        "fpm_stitch_tiles": (C.c_int, [C.c_int, vp, C.POINTER(fpm_stitch_grid), C.c_uint32, vp,
+                                       C.POINTER(C.c_double), vp, C.POINTER(C.c_double)]),
+        "fpm_stitch": (C.c_int, [vp, C.POINTER(fpm_stitch_grid), C.c_uint32, vp, C.POINTER(C.c_double),
+                                 C.POINTER(C.c_double)]),
         "fpm_runFPM": (C.c_int, [C.POINTER(fpm_problem), C.c_int, u16p, C.c_int,
                                  f32p, f32p, f32p, f32p]),
         "fpm_upload_frames": (C.c_int, [vp, C.POINTER(fpm_frames), vp, C.c_int, C.POINTER(C.c_int16)]),
@@ -501,6 +516,26 @@ class Solver:
         device memory of the caller's; None / 0 skips one."""
         _check(_lib.fpm_download_state_device(self._h, C.c_void_p(objF_ptr or 0), C.c_void_p(pupil_ptr or 0)))
 
+    def stitch(self, grid, stride, align: str = "none", device_ptr: int | None = None):
+        """fpm_stitch: the context's objCrop tiles (n_patch == gy * gx, row-major)
+        at strides `stride` (one int, or (stride_y, stride_x), in high-resolution
+        pixels, ceil(L/2) .. L) aligned ("none" | "phase" | "complex") and
+        blended into one field.  Returns (field, factors): field complex64
+        [H][W] (stitch_shape), or None when device_ptr names device memory of
+        the caller's that receives it; factors complex128 [n_patch].  Read-only
+        on the context, blocking."""
+        g = _stitch_grid(grid, self.prob.L, stride)
+        flags = _stitch_flags(align)
+        field = None
+        if device_ptr is None:
+            field = np.empty(tuple(max(v, 0) for v in stitch_shape(grid, self.prob.L, stride)), np.complex64)
+            dst = field.ctypes.data_as(C.c_void_p)
+        else:
+            dst, flags = C.c_void_p(device_ptr), flags | STITCH_DEVICE
+        fac = np.empty(max(g.gy * g.gx, 1), np.complex128)
+        _check(_lib.fpm_stitch(self._h, C.byref(g), flags, dst, fac.ctypes.data_as(C.POINTER(C.c_double)), None))
+        return field, fac
+
     def download_objcrop_device(self, ptr: int):
         _check(_lib.fpm_download_objcrop_device(self._h, C.c_void_p(ptr)))
 
@@ -615,6 +650,71 @@ def debug_plan_objcrop(L: int, fp16: bool = False, no_crop4k: bool = False) -> d
     o = fpm_objcrop_plan()
     _check(lib.fpm_debug_plan_objcrop(int(L), int(fp16), int(no_crop4k), C.byref(o)))
     return o.as_dict()
+
+
+def _stitch_strides(stride):
+    sy, sx = (stride, stride) if np.ndim(stride) == 0 else stride
+    return int(sy), int(sx)
+
+
+def _stitch_grid(grid, L, stride) -> fpm_stitch_grid:
+    gy, gx = grid
+    sy, sx = _stitch_strides(stride)
+    return fpm_stitch_grid(int(gy), int(gx), int(L), sy, sx)
+
+
+def _stitch_flags(align: str) -> int:
+    if align not in STITCH_ALIGN:
+        raise ValueError(f"align {align!r}: one of {sorted(STITCH_ALIGN)}")
+    return STITCH_ALIGN[align]
+
+
+def stitch_shape(grid, L: int, stride) -> tuple:
+    """(H, W) of the field of a (gy, gx) grid of L x L tiles at strides `stride`."""
+    sy, sx = _stitch_strides(stride)
+    return (int(grid[0]) - 1) * sy + int(L), (int(grid[1]) - 1) * sx + int(L)
+
+
+def stitch_tiles_device(tiles_ptr: int, field_ptr: int, grid, L: int, stride, align: str = "none", device: int = 0,
+                        stream_ptr: int | None = None):
+    """fpm_stitch_tiles with FPM_STITCH_DEVICE: tiles [gy*gx][L][L] and field
+    [H][W] (stitch_shape), float32 pairs, in device memory on `device`; the
+    tiles are read in place.  Returns (factors complex128 [gy*gx], the kernels'
+    event time in ms).  Blocking."""
+    lib = load_library()
+    g = _stitch_grid(grid, L, stride)
+    fac = np.empty(max(g.gy * g.gx, 1), np.complex128)
+    ms = C.c_double()
+    _check(lib.fpm_stitch_tiles(int(device), C.c_void_p(tiles_ptr or 0), C.byref(g), _stitch_flags(align) | STITCH_DEVICE,
+                                C.c_void_p(field_ptr or 0), fac.ctypes.data_as(C.POINTER(C.c_double)),
+                                C.c_void_p(stream_ptr or 0), C.byref(ms)))
+    return fac, ms.value
+
+
+def stitch_tiles(tiles, grid, stride, align: str = "none", device: int = 0):
+    """fpm_stitch_tiles on host arrays: tiles complex64 [gy*gx][L][L] (or
+    float32 with a trailing axis of 2), tile t = i*gx + j at rows i*stride_y,
+    columns j*stride_x.  Returns (field complex64 [H][W], factors complex128
+    [gy*gx]).  Blocking; the GPU does the work (device scratch of the call)."""
+    lib = load_library()
+    a = np.asarray(tiles)
+    if a.dtype == np.float32 and a.ndim == 4 and a.shape[-1] == 2:
+        a = np.ascontiguousarray(a).view(np.complex64)[..., 0]
+    if a.dtype != np.complex64 or a.ndim != 3 or a.shape[1] != a.shape[2]:
+        raise ValueError(f"tiles {a.dtype} {a.shape}: want complex64 [P][L][L]")
+    a = np.ascontiguousarray(a)
+    if a.shape[0] != int(grid[0]) * int(grid[1]):
+        raise ValueError(f"{a.shape[0]} tiles for a {grid[0]}x{grid[1]} grid")
+    L = a.shape[1]
+    g = _stitch_grid(grid, L, stride)
+    flags = _stitch_flags(align)
+    H, W = stitch_shape(grid, L, stride)
+    field = np.empty((max(H, 0), max(W, 0)), np.complex64)
+    fac = np.empty(a.shape[0], np.complex128)
+    _check(lib.fpm_stitch_tiles(int(device), a.ctypes.data_as(C.c_void_p), C.byref(g), flags,
+                                field.ctypes.data_as(C.c_void_p), fac.ctypes.data_as(C.POINTER(C.c_double)),
+                                None, None))
+    return field, fac
 
 
 def normalised_residual(d) -> np.ndarray:

@@ -5,8 +5,11 @@ the LED position, fpmMain.cpp:146-168), so a field of P patches is split into
 contiguous blocks, one per rank, with no collective inside an iteration.  The
 only exchange is one gather of every rank's high-resolution tiles to rank 0
 after the last iteration, followed by placing tile i at its (row, column) of
-the patch grid: tiles do not overlap, so stitching is pure placement.  The
-reference processes a single patch, so stitching is new here.
+the patch grid.  Tiles cut at a stride of a whole tile do not overlap, so
+stitching them is pure placement (stitch); tiles cut with an overlap are
+brought to a common phase and feathered together on the GPU (stitch_blend,
+fpm_stitch_tiles).  The reference processes a single patch, so stitching is
+new here.
 
 torch.distributed carries the gather (backend "nccl" = RCCL over xGMI on the
 GPU box, "gloo" in the CPU tests); nothing here touches the solver itself.
@@ -69,3 +72,38 @@ def stitch(tiles, grid: tuple[int, int]):
     rest = tuple(tiles.shape[3:])
     out = tiles.reshape((gy, gx, L, L) + rest).swapaxes(1, 2).reshape((gy * L, gx * L) + rest)
     return np.ascontiguousarray(out) if isinstance(out, np.ndarray) else out.contiguous()
+
+
+def stitch_blend(tiles, grid: tuple[int, int], stride, align: str = "none"):
+    """Blend OVERLAPPING tiles [P, L, L(, 2)] (row-major patch order) cut at
+    strides `stride` (an int or (stride_y, stride_x), ceil(L/2) .. L) into one
+    field: neighbours are brought to a common phase (align="phase") or phase
+    and scale ("complex") from the pixels they share and feathered together
+    (fpm_stitch_tiles, fpm_hip.h).  Returns (field,
+    factors), factors complex128 [P].
+
+    A torch tensor on the GPU (e.g. the gathered tiles on rank 0) is read in
+    place and the field is a torch tensor on the same device, of the tiles'
+    layout (complex64 [H, W] or float32 [H, W, 2]); a numpy array goes through
+    the host path.  At stride L without alignment the field is stitch()'s."""
+    import fpm_amd
+    gy, gx = grid
+    if tiles.shape[0] != gy * gx:
+        raise ValueError(f"{tiles.shape[0]} tiles for a {gy}x{gx} grid")
+    if isinstance(tiles, np.ndarray):
+        return fpm_amd.stitch_tiles(tiles, grid, stride, align)
+    import torch
+    if not tiles.is_cuda:
+        raise ValueError("stitch_blend: a torch tensor must be on the GPU (numpy arrays take the host path)")
+    pairs = not tiles.is_complex()
+    if (tiles.dtype != (torch.float32 if pairs else torch.complex64) or tiles.dim() != (4 if pairs else 3)
+            or (pairs and tiles.shape[-1] != 2) or tiles.shape[1] != tiles.shape[2]):
+        raise ValueError(f"tiles {tiles.dtype} {tuple(tiles.shape)}: want complex64 [P, L, L] or float32 [P, L, L, 2]")
+    t = tiles.contiguous()
+    L = t.shape[1]
+    H, W = fpm_amd.stitch_shape(grid, L, stride)
+    field = torch.empty((H, W, 2) if pairs else (H, W), dtype=t.dtype, device=t.device)
+    dev = t.device.index if t.device.index is not None else torch.cuda.current_device()
+    stream = torch.cuda.current_stream(t.device).cuda_stream
+    fac, _ = fpm_amd.stitch_tiles_device(t.data_ptr(), field.data_ptr(), grid, L, stride, align, dev, stream)
+    return field, fac

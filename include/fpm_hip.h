@@ -39,11 +39,13 @@ extern "C" {
  * caller sees, so the revision stands and each addition has a feature macro:
  * FPM_HAS_LED_CALIBRATION = fpm_residual_at, fpm_set_crops, fpm_get_crops;
  * FPM_HAS_LED_GAINS = fpm_set_gains, fpm_get_gains, fpm_moments;
- * FPM_HAS_STATE = fpm_set_state, fpm_download_state_device. */
+ * FPM_HAS_STATE = fpm_set_state, fpm_download_state_device;
+ * FPM_HAS_STITCH = fpm_stitch_tiles, fpm_stitch. */
 #define FPM_ABI_VERSION   6
 #define FPM_HAS_LED_CALIBRATION 1
 #define FPM_HAS_LED_GAINS 1
 #define FPM_HAS_STATE 1
+#define FPM_HAS_STITCH 1
 
 #define FPM_OK            0
 #define FPM_ERR_INVAL   (-22)   /* bad argument / unsupported geometry      */
@@ -360,6 +362,71 @@ int  fpm_set_state(fpm_ctx *ctx, const float *objF, const float *pupil, uint32_t
  * and blocking.  Either pointer may be NULL, not both.  FPM_ERR_STATE before a
  * state exists; FPM_ERR_INVAL on a capturing stream. */
 int  fpm_download_state_device(fpm_ctx *ctx, float *objF_dev, float *pupil_dev);
+
+/* Stitch a regular grid of overlapping tiles into one field: neighbours are
+ * brought to a common phase (and scale) from the pixels they share, then
+ * feathered together.  Every patch of a patch-wise reconstruction is its own
+ * phase-retrieval problem, defined up to a complex constant, and carries FFT
+ * wrap-around error along its border; side by side the tiles show seams.
+ * Geometry.  Tiles T[t], t = i*gx + j, each tile x tile (= L) complex, tile
+ * (i, j) at rows [i*stride_y, i*stride_y + L), columns [j*stride_x, ...).  The
+ * field is H x W, H = (gy-1)*stride_y + L, W = (gx-1)*stride_x + L.  Strides
+ * lie in [ceil(L/2), L], so a pixel is under at most two tiles per axis.
+ * Weights.  w = wy(i, y) wx(j, x); along an axis with overlap V = L - stride
+ * and local coordinate u: (u+1)/(V+1) for u < V when the tile has a lower
+ * neighbour, (L-u)/(V+1) for u >= stride when it has an upper one, else 1.
+ * The weights over a pixel sum to 1: nothing is divided.
+ * Factors.  f[0] = 1; the others in raster order from the left and the upper
+ * neighbour n.  Over the pixels a pair (n, t) shares, unweighted:
+ *   c = sum T[n] conj(T[t]),  a = sum |T[n]|^2,  b = sum |T[t]|^2
+ *   z = sum_n f[n] c,  num = sum_n |f[n]|^2 a,  den = sum_n b
+ *   FPM_STITCH_ALIGN_PHASE    f[t] = z / |z|
+ *   FPM_STITCH_ALIGN_COMPLEX  f[t] = (z / |z|) sqrt(num / den)
+ *   neither flag              every f = 1, the sums are not computed
+ *   z == 0 or den == 0        f[t] = 1
+ * The sums are accumulated in double on the GPU in a fixed order (no
+ * floating-point atomics), the solve runs in double on the host.
+ * Field.  out(y, x) = sum_t w_t f32(f[t]) T[t] over the covering tiles in
+ * ascending t, in fp32.  A pixel under one tile whose factor is exactly 1 is a
+ * copy of that tile's bits, so strides of L without alignment are pure
+ * placement.  Two calls return the same bits.
+ *   tiles   [gy*gx][L][L][2]
+ *   field   [H][W][2]; must not overlap tiles
+ *   factors [gy*gx][2] double (re, im), host memory; may be NULL
+ * Host pointers are staged through device scratch the call allocates and
+ * frees; with FPM_STITCH_DEVICE tiles and field are device memory on `device`,
+ * the tiles are read in place and nothing crosses PCIe but the pair sums and
+ * the factors.  hip_stream: the hipStream_t the work is enqueued on (NULL = the
+ * null stream).  Blocking.  The call makes `device` the calling thread's
+ * current device (hipSetDevice) and leaves it so, as every call on a context
+ * does for the context's device.  elapsed_ms (may be NULL): event-to-event time of
+ * the kernels (pair sums + blend; not the copies or the solve).
+ * FPM_ERR_INVAL, the message naming the field at fault: a NULL grid, tiles or
+ * field; gy or gx < 1; tile < 2; a stride outside [ceil(L/2), L]; both align
+ * flags, or an unknown flag; a capturing stream (before anything is enqueued);
+ * a grid past what the launches index (tile > 32768, more than 16384 tiles or
+ * 262140 field rows). */
+typedef struct fpm_stitch_grid {
+    int32_t gy, gx;        /* tiles per column / per row, tile t = i*gx + j          */
+    int32_t tile;          /* L                                                       */
+    int32_t stride_y, stride_x;   /* ceil(L/2) .. L                                   */
+} fpm_stitch_grid;
+#define FPM_STITCH_ALIGN_PHASE   1u
+#define FPM_STITCH_ALIGN_COMPLEX 2u   /* phase and scale; excludes ALIGN_PHASE        */
+#define FPM_STITCH_DEVICE        4u   /* tiles / field are device memory on `device`  */
+int  fpm_stitch_tiles(int device, const float *tiles, const fpm_stitch_grid *g, uint32_t flags,
+                      float *field, double *factors, void *hip_stream, double *elapsed_ms);
+
+/* The same for the context's own objCrop tiles (refreshed first, as
+ * fpm_download does), on the run stream: gy*gx == n_patch and tile == nlarge,
+ * else FPM_ERR_INVAL.  FPM_STITCH_DEVICE then describes `field` only (device
+ * memory on the context's device, clear of the context's own buffers: a
+ * field that overlaps the objCrop tiles is FPM_ERR_INVAL).  Read-only on the context: spectrum, pupil,
+ * maxima, fpm_timing and fpm_clock are untouched, and nothing it allocates
+ * stays in fpm_info.device_bytes.  Blocking.  FPM_ERR_STATE before a state
+ * exists; FPM_ERR_INVAL on a capturing stream, before anything is enqueued. */
+int  fpm_stitch(fpm_ctx *ctx, const fpm_stitch_grid *g, uint32_t flags, float *field,
+                double *factors, double *elapsed_ms);
 
 /* Use a caller-provided hipStream_t (NULL = the context's own stream). */
 int  fpm_set_stream(fpm_ctx *ctx, void *hip_stream);
