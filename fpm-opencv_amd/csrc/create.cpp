@@ -431,7 +431,8 @@ const char *plan_difference(const fpm_ctx *a, const fpm_ctx *b) {
     if (a->st.npart != b->st.npart) return "the pupil-maximum partials";
     const ResidualPlan &p = a->rplan, &q = b->rplan;
     if (p.kind != q.kind || p.nblk != q.nblk || p.nl != q.nl || p.t_led != q.t_led || !same_kernel(p.rows, q.rows) ||
-        !same_kernel(p.cols, q.cols) || !same_kernel(p.cols_gain, q.cols_gain) || !same_kernel(p.cols_mom, q.cols_mom))
+        !same_kernel(p.cols, q.cols) || !same_kernel(p.cols_gain, q.cols_gain) || !same_kernel(p.cols_mom, q.cols_mom) ||
+        !same_kernel(p.cols_pred, q.cols_pred))
         return "the residual sweep's plan";
     for (int g = 0; !a->fused() && g < a->ngroups; ++g) {
         const GeneralPlan &u = a->gplan[g], &v = b->gplan[g];
@@ -626,7 +627,7 @@ int fpm_debug_plan_ladder(int np, int nb, int B, int step, int no_wave_cols, int
     st.np = np;
     st.nb = nb;
     st.B = B;
-    StepKernel rows, cols, cols_gain, cols_mom;
+    StepKernel rows, cols, cols_gain, cols_mom, cols_pred;
     LdsLadder l;
     size_t row_static;
     if (step) {
@@ -635,7 +636,7 @@ int fpm_debug_plan_ladder(int np, int nb, int B, int step, int no_wave_cols, int
         row_static = std::max(p.k1.lds_static, p.k3.lds_static);
     } else {
         l = plan_lds_ladder(pl, np, nb, B, sw, false);
-        residual_lds_kernels(l, rows, cols, cols_gain, cols_mom);
+        residual_lds_kernels(l, rows, cols, cols_gain, cols_mom, cols_pred);
         row_static = rows.lds_static;
     }
     out->rows = ladder_kernel(rows, l.row_e, 0, row_static);
@@ -692,7 +693,7 @@ int fpm_debug_get_ladder(const fpm_ctx *c, int residual, fpm_ladder *out) {
         HIP_TRY(hipSetDevice(c->device));
         int rc = static_lds_matches(p.rows);
         if (rc || (rc = static_lds_matches(p.cols)) || (rc = static_lds_matches(p.cols_gain)) ||
-            (rc = static_lds_matches(p.cols_mom)))
+            (rc = static_lds_matches(p.cols_mom)) || (rc = static_lds_matches(p.cols_pred)))
             return rc;
         out->rows = ladder_kernel(p.rows, p.ladder.row_e, 0, p.rows.lds_static);
         out->cols = ladder_kernel(p.cols, p.ladder.col_e, p.ladder.cw, p.cols.lds_static);

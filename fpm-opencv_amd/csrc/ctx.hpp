@@ -4,7 +4,7 @@
 //                 fpm_set_gains / fpm_get_gains
 //   transfer.cpp  the stack uploads and the downloads
 //   run.cpp       fpm_init, fpm_run, the general path's patch groups and graphs
-//   residual_api.cpp  fpm_residual, fpm_residual_at, fpm_moments (kernels: residual.hip)
+//   residual_api.cpp  fpm_residual, fpm_residual_at, fpm_moments, fpm_predict (kernels: residual.hip)
 //   state_api.cpp fpm_set_state, fpm_download_state_device (kernels: state.hip)
 //   stitch_api.cpp fpm_stitch_tiles, fpm_stitch (kernels: stitch.hip; solve: stitch_solve.hpp)
 //   api.cpp       errors, version, info, timing, clock, fpm_runFPM
@@ -149,6 +149,10 @@ struct fpm_ctx {
     // fpm_moments' own: the per-block partials and the folded sums of C
     double *res_pcross = nullptr, *res_cross = nullptr;
     bool mom_ready = false;
+    // fpm_predict's staging buffer of one launch's images [nl][B][Np][Np] (4-byte
+    // elements), allocated by its first call with a host output
+    uint32_t *pred_stage = nullptr;
+    bool pred_ready = false;        // cols_pred may take its LDS (allow_large_lds)
     // fpm_set_state's check scratch, allocated by its first call
     fpm::StateCheck *state_chk = nullptr;
 

@@ -31,7 +31,8 @@
 // lines that differ stand under if constexpr or behind residual_dev.hpp's
 // overloads (res_led, res_T); the StepArgs instances are instruction for
 // instruction what the kernels were before they became templates
-// (tools/cmp_asm.py --pair).  plan_lds_ladder picks the generation and the
+// (tools/cmp_asm.py --pair).  PredArgs (fpm_predict) is the sweep with K2's
+// tail storing the pixels instead of summing them.  plan_lds_ladder picks the generation and the
 // launch shapes for both.
 //
 // Pruning: P vanishes outside the support disk, so the inverse transform has
@@ -90,7 +91,7 @@ __global__ void __launch_bounds__(256) k_gather_rowifft(DevState st, A a, FftPla
 // ---- K2 ---------------------------------------------------------------------
 // grid (Np, B), block 256, LDS 2*Np float2. One column per block.
 template <class A>
-constexpr size_t kLdsColpass = kIsRes<A> ? kResPartialLds<4> : 0;  // res_block_partial
+constexpr size_t kLdsColpass = kIsRes<A> && !kIsPred<A> ? kResPartialLds<4> : 0;  // res_block_partial
 template <class A>
 __global__ void __launch_bounds__(256) k_colpass(DevState st, A a, FftPlan pl,
                                                  const float2 *__restrict__ tw) {
@@ -112,7 +113,23 @@ __global__ void __launch_bounds__(256) k_colpass(DevState st, A a, FftPlan pl,
     float2 *oth = (res == bufa) ? bufb : bufa;
     const float inv_n2 = 1.0f / ((float)np * (float)np);
     const uint16_t *I = st.meas + ((size_t)sa.led * st.mB + b) * np * np;
-    if constexpr (kIsRes<A>) {
+    if constexpr (kIsPred<A>) {
+        // fpm_predict: the column's pixels stored at stride Np (the fallback of
+        // sizes where not even two columns fit a block); the stack is read by
+        // DIFF alone, where it lies
+        const int g = st.meas_g, npg = g ? np / g : 1;
+        const float rg = 1.0f / (float)(g ? g : 1);
+        const bool rd = pred_reads_stack(a);  // uniform
+        const size_t o = pred_image(a, z, st.B, b, np) + x;
+        for (int y = threadIdx.x; y < np; y += blockDim.x) {
+            unsigned iv = 0;
+            if (rd) {
+                const int m = udiv(y, g ? g : 1, rg), t = y - m * g;  // g > 0: y = t + g m
+                iv = g ? I[(size_t)x * np + t * npg + m] : I[(size_t)y * np + x];
+            }
+            pred_store(a, o + (size_t)y * np, pred_value(a, res[y], inv_n2, rg_led, iv));
+        }
+    } else if constexpr (kIsRes<A>) {
         const int g = st.meas_g;
         ResAcc<A> acc(rg_led);
         if (g) {  // uniform: the stored column x is contiguous, position p holds row (p mod (Np/g)) g + p / (Np/g)
@@ -391,7 +408,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
 // block NT (256 when the tile fits its register-lifted passes, so a 16 x 200
 // tile keeps every wave busy instead of idling half of a 512-thread block).
 template <int NT, class A>
-constexpr size_t kLdsColpassTiled = kIsRes<A> ? kResPartialLds<NT / 64> : 0;  // res_block_partial
+constexpr size_t kLdsColpassTiled = kIsRes<A> && !kIsPred<A> ? kResPartialLds<NT / 64> : 0;  // res_block_partial
 template <int NT, int E, class A>
 __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16 ? 4 : 1))) k_colpass_tiled(DevState st, A a, FftPlan pl,
                                                       const float2 *__restrict__ tw, int lc) {
@@ -416,7 +433,25 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
     tile_transform<true, NT, E>(tile, pl, lc, stw);
     const float inv_n2 = 1.0f / ((float)np * (float)np);
     const uint16_t *I = st.meas + ((size_t)sa.led * st.mB + b) * np * np;
-    if constexpr (kIsRes<A>) {
+    if constexpr (kIsPred<A>) {
+        // fpm_predict: the sums' walk below (rows in natural order, the tile's C
+        // columns across adjacent lanes), each row's columns stored as one
+        // segment of C elements; the stack is read by DIFF alone
+        const int g = st.meas_g, npg = g ? np / g : 1;
+        const float rg = 1.0f / (float)(g ? g : 1);
+        const bool rd = pred_reads_stack(a);  // uniform
+        const size_t o = pred_image(a, z, st.B, b, np) + x0;
+        for (int idx = threadIdx.x; idx < np * C; idx += NT) {
+            const int y = idx >> lc, c = idx & cm;
+            if (c >= cs) continue;
+            unsigned iv = 0;
+            if (rd) {
+                const int m = udiv(y, g ? g : 1, rg), t = y - m * g;  // g > 0: y = t + g m
+                iv = g ? I[(size_t)(x0 + c) * np + t * npg + m] : I[(size_t)y * np + x0 + c];
+            }
+            pred_store(a, o + (size_t)y * np + c, pred_value(a, tile[idx], inv_n2, rg_led, iv));
+        }
+    } else if constexpr (kIsRes<A>) {
         // rows in natural order, the tile's C columns across adjacent lanes (no
         // LDS bank conflict).  The stack is read as C*2-byte row segments in
         // the C-ABI layout; in a column layout row y of column x lies at
@@ -465,7 +500,7 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
 // the inverse transform, so their latency hides behind it.
 // grid (ceil(Np / (NW*CW)), B), block 64*NW, LDS (NW*CW*pitch + Np) float2
 template <int NW, class A>
-constexpr size_t kLdsColpassWave = kIsRes<A> ? kResPartialLds<NW> : 0;  // res_block_partial
+constexpr size_t kLdsColpassWave = kIsRes<A> && !kIsPred<A> ? kResPartialLds<NW> : 0;  // res_block_partial
 template <int NW, int CW, class A>
 __global__ void __launch_bounds__(64 * NW)
 k_colpass_wave(DevState st, A a, FftPlan pl, const float2 *__restrict__ tw, int P) {
@@ -485,8 +520,10 @@ k_colpass_wave(DevState st, A a, FftPlan pl, const float2 *__restrict__ tw, int 
     float2 *T = res_T(st, a, z, b, 0, np);
     // this lane's measurement values: rows lane + 64q of the wave's columns
     const uint16_t *I = st.meas + ((size_t)sa.led * st.mB + b) * np * np;
-    typename std::conditional<kIsRes<A>, unsigned, uint16_t>::type iv[NQY * CW];
-    if constexpr (kIsRes<A>) {
+    [[maybe_unused]] typename std::conditional<kIsRes<A>, unsigned, uint16_t>::type iv[NQY * CW];
+    if constexpr (kIsPred<A>) {
+        // fpm_predict reads the stack in its tail, for DIFF alone, in the order it stores
+    } else if constexpr (kIsRes<A>) {
         // the sweep reads the stack where it lies: every load issued before the
         // first use (clamped in-bounds, masked afterwards); in a column layout
         // row y of column x lies at x Np + (y mod g)(Np / g) + y / g
@@ -527,7 +564,26 @@ k_colpass_wave(DevState st, A a, FftPlan pl, const float2 *__restrict__ tw, int 
     __syncthreads();
     wave_transform<true, LPC>(cb, pl, stw, l);
     const float inv_n2 = 1.0f / ((float)np * (float)np);
-    if constexpr (kIsRes<A>) {
+    if constexpr (kIsPred<A>) {
+        // fpm_predict: the block's tile walked as the step's write-back walks
+        // it, rows in natural order with the C columns across adjacent lanes, so
+        // each row's columns leave as one segment of C elements
+        __syncthreads();
+        const int g = st.meas_g, npg = g ? np / g : 1;
+        const float rg = 1.0f / (float)(g ? g : 1);
+        const bool rd = pred_reads_stack(a);  // uniform
+        const size_t o = pred_image(a, z, st.B, b, np) + x0;
+        for (int idx = threadIdx.x; idx < np * C; idx += NT) {
+            const int y = udiv(idx, C, rC), c = idx - y * C;
+            if (c >= cs) continue;
+            unsigned iv1 = 0;
+            if (rd) {
+                const int m = udiv(y, g ? g : 1, rg), t = y - m * g;  // g > 0: y = t + g m
+                iv1 = g ? I[(size_t)(x0 + c) * np + t * npg + m] : I[(size_t)y * np + x0 + c];
+            }
+            pred_store(a, o + (size_t)y * np + c, pred_value(a, smem[c * P + y], inv_n2, rg_led, iv1));
+        }
+    } else if constexpr (kIsRes<A>) {
         ResAcc<A> acc(rg_led);
 #pragma unroll
         for (int q = 0; q < NQY; ++q) {
@@ -616,7 +672,7 @@ LdsLadder plan_lds_ladder(const FftPlan &pl, int np, int nb, int B, const Switch
 // the ladder's K1 / K2 for the update step (A = StepArgs) or the sweep (ResArgs)
 template <class A>
 static void pick_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols) {
-    if constexpr (!kIsMom<A> && !kIsGainRes<A>) {  // the row kernels have no tail: every sweep launches the ResArgs ones
+    if constexpr (!kIsMom<A> && !kIsGainRes<A> && !kIsPred<A>) {  // the row kernels have no tail: every sweep launches the ResArgs ones
         rows = l.rows;
         rows.fn = l.row_e == 16 ? (const void *)k_gather_rowifft_tiled<256, 16, A>
                   : l.row_e     ? (const void *)k_gather_rowifft_tiled<256, 24, A>
@@ -665,9 +721,10 @@ GeneralPlan plan_general_step(const DevState &st, GeneralPlan::Kind kind, const 
 }
 
 void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols, StepKernel &cols_gain,
-                          StepKernel &cols_mom) {
-    pick_lds_kernels<GainResArgs>(l, rows, cols_gain);  // (rows untouched by these two)
+                          StepKernel &cols_mom, StepKernel &cols_pred) {
+    pick_lds_kernels<GainResArgs>(l, rows, cols_gain);  // (rows untouched by these three)
     pick_lds_kernels<MomArgs>(l, rows, cols_mom);
+    pick_lds_kernels<PredArgs>(l, rows, cols_pred);
     pick_lds_kernels<ResArgs>(l, rows, cols);
 }
 

@@ -138,9 +138,16 @@ struct ResArgs {
 //                E = sum (|psi| - g sqrt(I))^2 (fpm_set_gains)
 //   MomArgs      fpm_moments: perr / err hold Q = sum |psi|^2, pcross / cross
 //                C = sum |psi| sqrt(I) (null in a residual launch)
+//   PredArgs     fpm_predict: no sums at all, the tail stores every pixel of
+//                the image, out[entry - o0][patch][y][x] (perr .. nblk unused)
 struct GainResArgs : ResArgs {};
 struct MomArgs : ResArgs {
     double *pcross, *cross;
+};
+struct PredArgs : ResArgs {
+    void *out;      // [n][B][Np][Np] float (amplitude, diff) or uint16_t (counts)
+    unsigned kind;  // FPM_PREDICT_AMPLITUDE / _COUNTS / _DIFF: uniform over the launch
+    int o0;         // the entry index out's first row belongs to
 };
 // Which kernel pair a context's sweep launches and how many LEDs at a time;
 // decided with the rest of the context (plan_context: no HIP call).
@@ -150,7 +157,8 @@ struct ResidualPlan {
     StepKernel rows, cols;     // one LED's grid: the launch multiplies it by the batch
     StepKernel cols_gain;      // cols with the gained residual's tail and with the moments' (fpm_moments):
     StepKernel cols_mom;       //   the same launch shape
-    LdsLadder ladder;          // Lds only: the rung rows / cols were picked from
+    StepKernel cols_pred;      // cols with the pixel-storing tail (fpm_predict): no fold follows it
+    LdsLadder ladder;         // Lds only: the rung rows / cols were picked from
     int nblk;                  // column blocks = partials per (LED, patch)
     int nl;                    // LEDs per launch
     size_t t_led;              // complex elements of T per LED
@@ -159,14 +167,18 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
                            const Switches &sw);
 // the sweep's kernels are the step's, instantiated for ResArgs: the ladder's
 // K1 / K2 (general.hip) and the Np 256 register column kernel (np256.hip)
-enum class ResTail { Plain, Gain, Moments };
+enum class ResTail { Plain, Gain, Moments, Predict };
 void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols, StepKernel &cols_gain,
-                          StepKernel &cols_mom);
+                          StepKernel &cols_mom, StepKernel &cols_pred);
 const void *residual_cols256_kernel(ResTail tail);
 // rows, columns and fold of the nl entries ra.ent[ra.i0 ...] with the column
 // kernel of `tail` (Moments: ra.pcross / ra.cross set, both folds)
 hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, const MomArgs &ra, ResTail tail, int nl,
                                  const float2 *tw, hipStream_t s);
+// rows and the pixel-storing columns of the nl entries pa.ent[pa.i0 ...]: entry
+// i's images go to pa.out's row i - pa.o0 (fpm_predict)
+hipError_t launch_predict_batch(const ResidualPlan &p, const DevState &st, const PredArgs &pa, int nl,
+                                const float2 *tw, hipStream_t s);
 
 // ---- batched transform of any length 2^a 3^b 5^c (fft_batch.hip)
 // Input band: sequences gs outside [qlo, qhi] and elements gi with

@@ -19,6 +19,8 @@
 //                      argument struct: for ResArgs it is the residual sweep's
 //                      column kernel (residual.hip), the same up to the column
 //                      IDFT for a batch of LEDs, then the residual sums
+//                      (PredArgs, fpm_predict: the pixels themselves, stored
+//                      as row segments of the block's 16 columns)
 //   R2 k_rows256_fwd   a block per 16-row tile row of the spectrum, a group
 //                      per box row: T row in, row DFT, object update and pupil
 //                      numerator on the row's disk pixels, then the tile
@@ -171,7 +173,17 @@ __global__ void __launch_bounds__(n256::NT) k_cols256(DevState st, A a, const fl
     // this group's measurement column, rows t + 16 m (meas_layout g = 16:
     // stored[x Np + 16 t + m] = I[t + 16 m][x]), two 16-byte loads per lane
     const uint4 *Ic = (const uint4 *)(st.meas + (((size_t)sa.led * st.mB + b) * N + x0 + g) * N + 16 * t);
-    const uint4 ia = Ic[0], ib = Ic[1];
+    uint4 ia, ib;
+    if constexpr (kIsPred<A>) {  // fpm_predict reads the stack for DIFF alone (uniform)
+        ia = ib = make_uint4(0, 0, 0, 0);
+        if (pred_reads_stack(a)) {
+            ia = Ic[0];
+            ib = Ic[1];
+        }
+    } else {
+        ia = Ic[0];
+        ib = Ic[1];
+    }
     // the box rows of the strip: 128-byte row segments, every load of a
     // thread issued before its LDS stores (clamped, masked)
     constexpr int KMAX = N * GPB / NT;  // nb <= N rows
@@ -200,7 +212,33 @@ __global__ void __launch_bounds__(n256::NT) k_cols256(DevState st, A a, const fl
     float2 y[16];
     dft256_full<true, true>(v, y, wt, LdsTw{twL, t, 1}, t, xrd);  // :365 (columns); y[m] = row t + 16 m
     const unsigned iw[8] = {ia.x, ia.y, ia.z, ia.w, ib.x, ib.y, ib.z, ib.w};
-    if constexpr (kIsRes<A>) {
+    if constexpr (kIsPred<A>) {
+        // fpm_predict: a lane holds rows t + 16 m of column x0 + g, so the
+        // block's N x GPB pixels are transposed through the exchange space (a
+        // float tile of pitch GPB + 1) and leave as one segment of GPB adjacent
+        // x per row: 64 bytes of float, 32 of uint16
+        constexpr int PP = GPB + 1;
+        static_assert((size_t)N * PP * sizeof(float) <= (size_t)GPB * XTILE_H * sizeof(float2),
+                      "the pixel tile fits the groups' exchange tiles (lds_cols)");
+        const float inv_n2 = 1.0f / ((float)N * (float)N);
+        float *pt = reinterpret_cast<float *>(strip);
+        float pv[16];
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+            const unsigned iv = (iw[m >> 1] >> (16 * (m & 1))) & 0xffffu;
+            pv[m] = pred_value(a, y[m], inv_n2, rg_led, iv);
+        }
+        __syncthreads();  // every group is done with its exchange tile
+#pragma unroll
+        for (int m = 0; m < 16; ++m) pt[(t + 16 * m) * PP + g] = pv[m];
+        __syncthreads();
+        const size_t o = pred_image(a, z, st.B, b, N) + x0 + t;
+#pragma unroll
+        for (int k = 0; k < N / GPB; ++k) {
+            const int row = g + GPB * k;
+            pred_store(a, o + (size_t)row * N, pt[row * PP + t]);
+        }
+    } else if constexpr (kIsRes<A>) {
         const float inv_n2 = 1.0f / ((float)N * (float)N);
         ResAcc<A> acc(rg_led);
 #pragma unroll
@@ -364,7 +402,8 @@ __global__ void __launch_bounds__(n256::NT) __attribute__((amdgpu_waves_per_eu(4
 }  // namespace
 
 const void *residual_cols256_kernel(ResTail tail) {
-    return tail == ResTail::Moments ? (const void *)k_cols256<MomArgs>
+    return tail == ResTail::Predict ? (const void *)k_cols256<PredArgs>
+           : tail == ResTail::Moments ? (const void *)k_cols256<MomArgs>
            : tail == ResTail::Gain  ? (const void *)k_cols256<GainResArgs>
                                     : (const void *)k_cols256<ResArgs>;
 }

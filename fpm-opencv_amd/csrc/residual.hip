@@ -21,7 +21,12 @@
 // above; GainResArgs, E under the LED gains, E = sum (|psi| - g sqrt(I))^2,
 // launched when some gain is not 1 (fpm_set_gains); MomArgs, the raw moments
 // Q = sum |psi|^2 and C = sum |psi| sqrt(I) beside S (fpm_moments).  One launch
-// shape, one row kernel and one fold serve all three.
+// shape, one row kernel and one fold serve all three.  A fourth, PredArgs
+// (fpm_predict), sums nothing: it stores |psi|, the counts a camera would
+// record or |psi| - g sqrt(I) of every pixel, the kind a uniform runtime
+// switch of the one instance, and reads the stack for the last kind only; it
+// shares the launch shape and the row kernel and has no fold
+// (launch_predict_batch).
 //
 // What is left in this file:
 //   k_res_rows256   the register pair's row kernel (Np 256, fp32 spectrum, the
@@ -143,13 +148,14 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
         const int Bp = xcd_patches(B);
         p.rows = StepKernel{(const void *)k_res_rows256, dim3(row_blocks(nb) * Bp), dim3(NT), lds_rows(), 0};
         p.cols = StepKernel{residual_cols256_kernel(ResTail::Plain), dim3(kColBlocks * Bp), dim3(NT), lds_cols(nb), 0};
-        p.cols_gain = p.cols_mom = p.cols;
+        p.cols_gain = p.cols_mom = p.cols_pred = p.cols;
         p.cols_gain.fn = residual_cols256_kernel(ResTail::Gain);
         p.cols_mom.fn = residual_cols256_kernel(ResTail::Moments);
+        p.cols_pred.fn = residual_cols256_kernel(ResTail::Predict);
         p.nblk = kColBlocks;
     } else {
         p.ladder = plan_lds_ladder(pl, np, nb, B, sw, false);
-        residual_lds_kernels(p.ladder, p.rows, p.cols, p.cols_gain, p.cols_mom);
+        residual_lds_kernels(p.ladder, p.rows, p.cols, p.cols_gain, p.cols_mom, p.cols_pred);
         p.nblk = (int)p.cols.grid.x;
     }
     // LEDs per launch: as many as the scratch cap holds (FPM_RES_BATCH=n forces n)
@@ -181,6 +187,26 @@ hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, cons
     }
     hipLaunchKernelGGL(k_res_fold, dim3((nl * st.B + 255) / 256), dim3(256), 0, s, ra, nl, st.B);
     return hipGetLastError();
+}
+
+// fpm_predict: the sweep's row kernel, then the column kernel whose tail stores
+// the pixels.  No partials and no fold.
+hipError_t launch_predict_batch(const ResidualPlan &p, const DevState &st, const PredArgs &pa_in, int nl,
+                                const float2 *tw, hipStream_t s) {
+    PredArgs pa = pa_in;
+    pa.nblk = p.nblk;
+    hipError_t e;
+    if (p.kind == ResidualPlan::Reg256) {  // the register kernels take no FftPlan
+        DevState sv = st;
+        void *rargs[] = {&sv, static_cast<ResArgs *>(&pa), &tw}, *cargs[] = {&sv, &pa, &tw};
+        e = hipLaunchKernel(p.rows.fn, dim3(p.rows.grid.x * nl), p.rows.block, rargs, p.rows.lds, s);
+        if (e != hipSuccess) return e;
+        return hipLaunchKernel(p.cols_pred.fn, dim3(p.cols_pred.grid.x * nl), p.cols_pred.block, cargs,
+                               p.cols_pred.lds, s);
+    }
+    e = launch_step_kernel(p.rows, st, static_cast<const ResArgs &>(pa), p.pl, tw, s, nl);
+    if (e != hipSuccess) return e;
+    return launch_step_kernel(p.cols_pred, st, pa, p.pl, tw, s, nl);
 }
 
 }  // namespace fpm

@@ -1,6 +1,7 @@
-// residual_api.cpp -- fpm_residual, fpm_residual_at and fpm_moments: the
-// data-fidelity residual of the current state, or the raw moments it is made
-// of (residual.hip), as a sequence of steps: refuse
+// residual_api.cpp -- fpm_residual, fpm_residual_at, fpm_moments and
+// fpm_predict: the data-fidelity residual of the current state, the raw
+// moments it is made of, or the predicted images themselves (residual.hip),
+// as a sequence of steps: refuse
 // a capturing stream, make sure the scratch exists, launch the batches of an
 // entry list between two events, copy the folded sums out, report the event
 // time.  One path: fpm_residual sweeps the context's identity list (every
@@ -83,13 +84,14 @@ int copy_sums(fpm_ctx *c, int n, double *err, double *ref, double *cross = nullp
     return FPM_OK;
 }
 
-// what every entry point checks before anything is enqueued
-int admit(fpm_ctx *c, const char *what, bool any_output) {
+// what every entry point checks before anything is enqueued; need_stack: the
+// call compares with the images (everything but fpm_predict's AMPLITUDE and COUNTS)
+int admit(fpm_ctx *c, const char *what, bool any_output, bool need_stack = true) {
     if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
     if (!any_output) return set_err(FPM_ERR_INVAL, "%s: every output pointer is NULL", what);
     if (!c->initialized) return set_err(FPM_ERR_STATE, "%s before fpm_init", what);
     // a state set by fpm_set_state on a context without a stack has no images to compare with
-    if (!c->uploaded) return set_err(FPM_ERR_STATE, "%s: no stack uploaded", what);
+    if (need_stack && !c->uploaded) return set_err(FPM_ERR_STATE, "%s: no stack uploaded", what);
     HIP_TRY(hipSetDevice(c->device));
     return refuse_capture(c, what);
 }
@@ -116,14 +118,11 @@ int sweep_identity(fpm_ctx *c, bool mom, double *err, double *ref, double *cross
     return finish(c, elapsed_ms);
 }
 
-// a probe list, after admit
-int sweep_probes(fpm_ctx *c, const char *what, bool mom, const fpm_probe *probes, int n, double *err, double *ref,
-                 double *cross, double *elapsed_ms) {
-    int rc;
+// a probe list as entries: every one resolved and validated before the first launch
+int resolve_probes(const fpm_ctx *c, const char *what, const fpm_probe *probes, int n, std::vector<ResEntry> &ent) {
     if (!probes || n < 1) return set_err(FPM_ERR_INVAL, "%s: %s", what, probes ? "n < 1" : "null probes");
-    // every entry resolved and validated before the first launch
     const int np = c->st.np, L = c->st.L, n_order = c->prob.n_order;
-    std::vector<ResEntry> ent((size_t)n);
+    ent.resize((size_t)n);
     for (int k = 0; k < n; ++k) {
         const fpm_probe &q = probes[k];
         if (q.pos < 0 || q.pos >= n_order)
@@ -135,6 +134,16 @@ int sweep_probes(fpm_ctx *c, const char *what, bool mom, const fpm_probe *probes
                            "spectrum", what, k, x, y, led, L, L);
         ent[k] = ResEntry{led, (int)x + np / 2, (int)y + np / 2, 0};
     }
+    return FPM_OK;
+}
+
+// a probe list, after admit
+int sweep_probes(fpm_ctx *c, const char *what, bool mom, const fpm_probe *probes, int n, double *err, double *ref,
+                 double *cross, double *elapsed_ms) {
+    std::vector<ResEntry> ent;
+    int rc = resolve_probes(c, what, probes, n, ent);
+    if (rc) return rc;
+    const int n_order = c->prob.n_order;
     if ((rc = mom ? ensure_moments_scratch(c) : ensure_scratch(c))) return rc;
     const size_t B = c->st.B;
     HIP_TRY(hipEventRecord(c->res_ev[0], c->stream));
@@ -155,7 +164,91 @@ int sweep_probes(fpm_ctx *c, const char *what, bool mom, const fpm_probe *probes
     return finish(c, elapsed_ms);
 }
 
+// fpm_predict's additions to the sweep's scratch: the staging buffer of one
+// launch's images, by the first call with a host output
+int ensure_predict_scratch(fpm_ctx *c, bool stage) {
+    int rc = ensure_scratch(c);
+    if (rc) return rc;
+    const ResidualPlan &p = c->rplan;
+    if (!c->pred_ready) {
+        HIP_TRY(allow_large_lds({&p.cols_pred}, c->lds_limit));
+        c->pred_ready = true;
+    }
+    if (stage && !c->pred_stage)
+        rc = dalloc(c, &c->pred_stage, (size_t)p.nl * c->st.B * c->st.np * c->st.np, false);
+    return rc;
+}
+
+// the images of a list (probes null: the identity list), after admit.  The list
+// runs in pieces of n_order entries (the entry table) and each piece nl
+// entries per launch, as the sweep's.  A device out takes the kernels' stores
+// as they are, one event pair around all launches; a host out takes each
+// launch's batch from the staging buffer before the next launch overwrites it,
+// so every launch has its own event pair and the copies lie between the pairs:
+// elapsed_ms is the kernels' time in both.
+int predict(fpm_ctx *c, const fpm_probe *probes, int n, unsigned kind, bool dev, void *out, double *elapsed_ms) {
+    std::vector<ResEntry> ent;
+    int rc;
+    const int n_order = c->prob.n_order;
+    if (!probes) n = n_order;
+    else if ((rc = resolve_probes(c, "fpm_predict", probes, n, ent))) return rc;
+    if ((rc = ensure_predict_scratch(c, !dev))) return rc;
+    const ResidualPlan &p = c->rplan;
+    const size_t img = (size_t)c->st.B * c->st.np * c->st.np, esz = kind == FPM_PREDICT_COUNTS ? 2 : 4;
+    char *const o = static_cast<char *>(out);
+    double ms_sum = 0.0;
+    if (dev) HIP_TRY(hipEventRecord(c->res_ev[0], c->stream));
+    for (int k0 = 0; k0 < n; k0 += n_order) {
+        const int m = std::min(n_order, n - k0);
+        const ResEntry *e = c->ident_dev;
+        if (probes) {  // (ent is pageable: the copy has left it when hipMemcpyAsync returns)
+            HIP_TRY(hipMemcpyAsync(c->res_ent, ent.data() + k0, (size_t)m * sizeof(ResEntry), hipMemcpyHostToDevice,
+                                   c->stream));
+            e = c->res_ent;
+        }
+        for (int i0 = 0; i0 < m; i0 += p.nl) {
+            const int nl = std::min(p.nl, m - i0);
+            PredArgs pa{};
+            pa.ent = e;
+            pa.i0 = i0;
+            pa.T = c->res_T;
+            pa.kind = kind;
+            pa.out = dev ? static_cast<void *>(o + (size_t)k0 * img * esz) : static_cast<void *>(c->pred_stage);
+            pa.o0 = dev ? 0 : i0;
+            if (!dev) HIP_TRY(hipEventRecord(c->res_ev[0], c->stream));
+            HIP_TRY(launch_predict_batch(p, c->st, pa, nl, c->tw_np, c->stream));
+            if (!dev) {
+                HIP_TRY(hipEventRecord(c->res_ev[1], c->stream));
+                HIP_TRY(hipMemcpyAsync(o + (size_t)(k0 + i0) * img * esz, c->pred_stage, (size_t)nl * img * esz,
+                                       hipMemcpyDeviceToHost, c->stream));
+                double ms = 0.0;
+                if ((rc = finish(c, &ms))) return rc;
+                ms_sum += ms;
+            }
+        }
+    }
+    if (dev) {
+        HIP_TRY(hipEventRecord(c->res_ev[1], c->stream));
+        return finish(c, elapsed_ms);
+    }
+    if (elapsed_ms) *elapsed_ms = ms_sum;
+    return FPM_OK;
+}
+
 }  // namespace
+
+extern "C" int fpm_predict(fpm_ctx *c, const fpm_probe *probes, int n, uint32_t flags, void *out,
+                           double *elapsed_ms) {
+    if (!c) return set_err(FPM_ERR_INVAL, "null ctx");
+    const uint32_t known = FPM_PREDICT_COUNTS | FPM_PREDICT_DIFF | FPM_PREDICT_DEVICE;
+    if (flags & ~known) return set_err(FPM_ERR_INVAL, "fpm_predict: unknown flag bits 0x%x", flags & ~known);
+    const unsigned kind = flags & (FPM_PREDICT_COUNTS | FPM_PREDICT_DIFF);
+    if (kind == (FPM_PREDICT_COUNTS | FPM_PREDICT_DIFF))
+        return set_err(FPM_ERR_INVAL, "fpm_predict: flags 0x%x name more than one kind (COUNTS and DIFF)", flags);
+    if (!out) return set_err(FPM_ERR_INVAL, "fpm_predict: out is NULL");
+    const int rc = admit(c, "fpm_predict", true, kind == FPM_PREDICT_DIFF);
+    return rc ? rc : predict(c, probes, n, kind, (flags & FPM_PREDICT_DEVICE) != 0, out, elapsed_ms);
+}
 
 extern "C" int fpm_residual(fpm_ctx *c, double *err, double *ref, double *elapsed_ms) {
     const int rc = admit(c, "fpm_residual", err || ref);

@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "cpk.hpp"
+#include "fpm_hip.h"
 #include "fpm_state.hpp"
 #include "launch.hpp"
 #include "np256_layout.hpp"
@@ -24,8 +25,12 @@ template <class A>
 constexpr bool kIsMom = std::is_same<A, MomArgs>::value;
 template <class A>
 constexpr bool kIsGainRes = std::is_same<A, GainResArgs>::value;
+// PredArgs (fpm_predict) shares the front half too and has no sums: its tail
+// stores every pixel (pred_value, pred_store below).
 template <class A>
-constexpr bool kIsRes = std::is_same<A, ResArgs>::value || kIsGainRes<A> || kIsMom<A>;
+constexpr bool kIsPred = std::is_same<A, PredArgs>::value;
+template <class A>
+constexpr bool kIsRes = std::is_same<A, ResArgs>::value || kIsGainRes<A> || kIsMom<A> || kIsPred<A>;
 
 // (|psi| - sqrt(I))^2 of one pixel added to acc: v = the unscaled IDFT value,
 // psi = v / Np^2 (the reference's ifft2 scaling), no eps.  I is exact and
@@ -64,9 +69,42 @@ __device__ __forceinline__ float res_add_gain(float acc, float2 v, float inv_n2,
 // at the update) or the moments.
 template <class A>
 __device__ __forceinline__ float res_gain(const DevState &st, int led, int b) {
-    if constexpr (kIsGainRes<A>) return led_gain(st, led, b);
+    if constexpr (kIsGainRes<A> || kIsPred<A>) return led_gain(st, led, b);
     else return 1.0f;
 }
+
+// ---- fpm_predict's tail: one pixel of the predicted image instead of a sum.
+// The kind is uniform over the launch, so each switch is a scalar branch.
+//   AMPLITUDE  |psi|, raw: the gain does not enter (as fpm_moments)
+//   COUNTS     what the camera would record, rint((|psi| / g)^2) saturated at
+//              65535 (half to even; an integer below 2^16, exact as a float)
+//   DIFF       |psi| - g sqrt(I); the product kept opaque as in res_add_gain,
+//              so g = 1.0f is bit for bit the ungained difference
+// I is read by DIFF alone: the callers load it under the same uniform branch.
+__device__ __forceinline__ bool pred_reads_stack(const PredArgs &pa) { return pa.kind == FPM_PREDICT_DIFF; }
+__device__ __forceinline__ float pred_value(const PredArgs &pa, float2 v, float inv_n2, float g, unsigned I) {
+    const float a = sqrtf(cabs2(v)) * inv_n2;
+    if (pa.kind == FPM_PREDICT_COUNTS) {
+        const float q = a / g;
+        return fminf(rintf(q * q), 65535.0f);
+    }
+    if (pa.kind == FPM_PREDICT_DIFF) {
+        float s = g * sqrtf((float)I);
+        asm("" : "+v"(s));
+        return a - s;
+    }
+    return a;
+}
+// the image of entry i0 + z and patch b in out, as an element offset, and the
+// store of pixel off of out: 2 bytes for the counts, else 4
+__device__ __forceinline__ size_t pred_image(const PredArgs &pa, int z, int B, int b, int np) {
+    return ((size_t)(pa.i0 + z - pa.o0) * B + b) * np * np;
+}
+__device__ __forceinline__ void pred_store(const PredArgs &pa, size_t off, float val) {
+    if (pa.kind == FPM_PREDICT_COUNTS) static_cast<uint16_t *>(pa.out)[off] = (uint16_t)val;
+    else static_cast<float *>(pa.out)[off] = val;
+}
+
 template <class A>
 struct ResAcc {
     float e = 0.f, g, g2;

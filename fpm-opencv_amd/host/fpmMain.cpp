@@ -78,6 +78,14 @@
 //                      patch sums of Q - 2 g C + g^2 S at the old and the new
 //                      gains), moments_ms.  Combines with --calibrate-leds (the
 //                      positions first) and --residual
+//   --write-predicted amplitude|counts|diff   the forward model's images of the
+//                      final state (fpm_predict), after the last iteration:
+//                      predicted.npy [used][patches][Np][Np] in processing order,
+//                      float32 |psi| (amplitude), uint16 rint((|psi| / g)^2)
+//                      saturated at 65535, what the camera would record (counts),
+//                      or float32 |psi| - g sqrt(I), the per-pixel mismatch with
+//                      the measurements (diff); result.json gains "predicted":
+//                      kind, shape, ms
 //   --init-pupil FILE.npy  start from this pupil instead of the support disk:
 //                      complex64 [Np][Np] (one pupil for every patch) or
 //                      [patches][Np][Np], centred as pupil.npy / pupils.npy are
@@ -151,6 +159,37 @@ bool write_npy_c64_3d(const std::string &path, const float *data, int n0, int n1
     fwrite(data, sizeof(float) * 2, (size_t)n0 * n1 * n2, f);
     return fclose(f) == 0;
 }
+
+// predicted.npy: float32 ('<f4') or uint16 ('<u2') [n0][n1][n2][n3]
+bool write_npy_4d(const std::string &path, const void *data, const char *descr, size_t elem, int n0, int n1, int n2,
+                  int n3) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) return false;
+    char dict[160];
+    snprintf(dict, sizeof dict, "{'descr': '%s', 'fortran_order': False, 'shape': (%d, %d, %d, %d), }", descr, n0, n1,
+             n2, n3);
+    std::string hdr = dict;
+    size_t pad = (64 - (10 + hdr.size() + 1) % 64) % 64;
+    hdr.append(pad, ' ');
+    hdr.push_back('\n');
+    const unsigned char magic[8] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0};
+    fwrite(magic, 1, 8, f);
+    const unsigned short hl = (unsigned short)hdr.size();
+    fwrite(&hl, 2, 1, f);
+    fwrite(hdr.data(), 1, hdr.size(), f);
+    fwrite(data, elem, (size_t)n0 * n1 * n2 * n3, f);
+    return fclose(f) == 0;
+}
+
+const char *kUsage =
+    "Usage: fpmMain dataset.json itrCount [options]\n"
+    "  --out DIR  --device N  --led-table FILE  --path general|fused|auto\n"
+    "  --grid GXxGY  --overlap V  --stitch-align none|phase|complex  --write-tiles\n"
+    "  --residual  --calibrate-leds R  --calibrate-gains\n"
+    "  --init-pupil FILE.npy  --init-objf FILE.npy\n"
+    "  --write-predicted amplitude|counts|diff\n"
+    "      predicted.npy [used][patches][Np][Np]: the forward model's image of every LED for the\n"
+    "      final state (float32 |psi|, uint16 counts, or float32 |psi| - g sqrt(I))\n";
 
 // A .npy file of little-endian complex64 in C order, format version 1.0 or
 // 2.0: its shape and its values as (re, im) pairs.  The header's shape must
@@ -280,6 +319,11 @@ bool read_led_table(const std::string &path, std::vector<float> *xyz) {
 }  // namespace
 
 int main(int argc, char **argv) {
+    for (int i = 1; i < argc; ++i)
+        if (std::string(argv[i]) == "--help") {
+            std::cout << kUsage;
+            return 0;
+        }
     if (argc < 3) {
         std::cout << "ERROR: Not enough input argumants.\n Usage: ./fpmMain dataset.json" << std::endl;
         return 0;
@@ -292,6 +336,7 @@ int main(int argc, char **argv) {
     int overlap = -1;          // --overlap V: low-resolution pixels neighbouring patches share (-1: not given)
     std::string stitch_align;  // --stitch-align none|phase|complex
     bool write_tiles = false;  // --write-tiles: objCrop_tiles.npy [B][L][L] as well
+    std::string predicted;     // --write-predicted amplitude|counts|diff: predicted.npy of the final state
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--out" && i + 1 < argc) out_dir = argv[++i];
@@ -318,6 +363,13 @@ int main(int argc, char **argv) {
         else if (a == "--init-pupil" && i + 1 < argc) init_pupil = argv[++i];
         else if (a == "--init-objf" && i + 1 < argc) init_objf = argv[++i];
         else if (a == "--residual") want_residual = true;
+        else if (a == "--write-predicted" && i + 1 < argc) {
+            predicted = argv[++i];
+            if (predicted != "amplitude" && predicted != "counts" && predicted != "diff") {
+                std::cerr << "--write-predicted wants amplitude, counts or diff" << std::endl;
+                return 2;
+            }
+        }
         else if (a == "--calibrate-gains") want_gains = true;
         else if (a == "--calibrate-leds" && i + 1 < argc) {
             cal_radius = atoi(argv[++i]);
@@ -664,6 +716,19 @@ int main(int argc, char **argv) {
             return 1;
         }
     }
+    // --write-predicted: the forward model's images of the final state (fpm_predict)
+    std::vector<uint32_t> pred;  // float32, or uint16 in the leading half
+    double pred_ms = 0;
+    if (!predicted.empty()) {
+        const uint32_t kind = predicted == "counts" ? FPM_PREDICT_COUNTS
+                              : predicted == "diff" ? FPM_PREDICT_DIFF
+                                                    : FPM_PREDICT_AMPLITUDE;
+        pred.resize((size_t)used * B * np * np);
+        if ((rc = fpm_predict(ctx, nullptr, 0, kind, pred.data(), &pred_ms))) {
+            std::cerr << "fpm: " << fpm_last_error() << std::endl;
+            return 1;
+        }
+    }
     fpm_info info;
     fpm_get_info_sized(ctx, &info, sizeof info);
     fpm_destroy(ctx);
@@ -691,6 +756,9 @@ int main(int argc, char **argv) {
              write_npy_c64_3d(out_dir + "/pupils.npy", pupil.data(), B, np, np);
     }
     if (ok && write_tiles) ok = write_npy_c64_3d(out_dir + "/objCrop_tiles.npy", objCrop.data(), B, L, L);
+    if (ok && !predicted.empty())
+        ok = write_npy_4d(out_dir + "/predicted.npy", pred.data(), predicted == "counts" ? "<u2" : "<f4",
+                          predicted == "counts" ? 2 : 4, used, B, np, np);
     if (ok) {  // JSON sidecar describing the arrays (replaces the reference's display windows)
         FILE *f = fopen((out_dir + "/result.json").c_str(), "w");
         ok = f != nullptr;
@@ -775,6 +843,9 @@ int main(int argc, char **argv) {
                 }
                 fprintf(f, "], \"moments_ms\": %.6f},\n", gain_ms);
             }
+            if (!predicted.empty())
+                fprintf(f, "  \"predicted\": {\"kind\": \"%s\", \"shape\": [%d, %d, %d, %d], \"ms\": %.6f},\n",
+                        predicted.c_str(), used, B, np, np, pred_ms);
             if (blend) {  // factors in row-major patch order, (re, im)
                 fprintf(f, "  \"stitch\": {\"overlap\": %d, \"stride\": %d, \"align\": \"%s\", \"field\": [%d, %d], "
                            "\"factors\": [", overlap, st_stride, stitch_align.c_str(), st_h, st_w);

@@ -43,6 +43,10 @@ STITCH_ALIGN_COMPLEX = 2    # phase and scale
 STITCH_DEVICE = 4           # tiles / field are device pointers
 STITCH_ALIGN = {"none": 0, "phase": STITCH_ALIGN_PHASE, "complex": STITCH_ALIGN_COMPLEX}
 
+# fpm_predict flags (fpm_hip.h FPM_PREDICT_*): one kind, optionally | PREDICT_DEVICE
+PREDICT_AMPLITUDE, PREDICT_COUNTS, PREDICT_DIFF, PREDICT_DEVICE = 0, 1, 2, 4
+PREDICT_KINDS = {"amplitude": PREDICT_AMPLITUDE, "counts": PREDICT_COUNTS, "diff": PREDICT_DIFF}
+
 # fpm_info.fused_kernel: the LED-update kernel of the context (fpm_hip.h FPM_KERNEL_*)
 KERNEL_GENERAL, KERNEL_FUSED_NP256, KERNEL_FUSED_NP200, KERNEL_FUSED_SMALL, KERNEL_FUSED_NP256_DIST = 0, 1, 2, 3, 4
 KERNEL_FUSED_NP90 = 5
@@ -59,7 +63,7 @@ HIP_SYMBOLS = (
     "fpm_upload_frames", "fpm_download_stack", "fpm_get_info_sized", "fpm_abi_version",
     "fpm_get_clock", "fpm_residual", "fpm_residual_at", "fpm_set_crops", "fpm_get_crops",
     "fpm_set_gains", "fpm_get_gains", "fpm_moments", "fpm_set_state", "fpm_download_state_device",
-    "fpm_stitch_tiles", "fpm_stitch",
+    "fpm_stitch_tiles", "fpm_stitch", "fpm_predict",
 )
 # test-only entry points (include/fpm_hip_debug.h)
 HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan",
@@ -199,6 +203,7 @@ def load_library(path: str = HIP_LIB):
         "fpm_set_gains": (C.c_int, [vp, f32p]),
         "fpm_get_gains": (C.c_int, [vp, f32p]),
         "fpm_moments": (C.c_int, [vp, C.POINTER(fpm_probe), C.c_int] + [C.POINTER(C.c_double)] * 4),
+        "fpm_predict": (C.c_int, [vp, C.POINTER(fpm_probe), C.c_int, C.c_uint32, vp, C.POINTER(C.c_double)]),
         "fpm_set_state": (C.c_int, [vp, vp, vp, C.c_uint32]),
         "fpm_download_state_device": (C.c_int, [vp, vp, vp]),
         "fpm_stitch_tiles": (C.c_int, [C.c_int, vp, C.POINTER(fpm_stitch_grid), C.c_uint32, vp,
@@ -416,6 +421,38 @@ class Solver:
         dp = C.POINTER(C.c_double)
         _check(_lib.fpm_moments(self._h, probes, n, *(a.ctypes.data_as(dp) for a in out), C.byref(ms)))
         return dict(model=out[0], cross=out[1], ref=out[2], ms=ms.value)
+
+    def predict(self, kind: str = "amplitude", pos=None, dx=None, dy=None, device_ptr: int | None = None):
+        """fpm_predict: the forward model's images of the current state,
+        [n][n_patch][Np][Np] with pixel (y, x) at [y][x].  kind "amplitude":
+        float32 |psi| (the gains do not enter); "counts": uint16
+        rint((|psi| / g)^2) saturated at 65535, what the camera would record;
+        "diff": float32 |psi| - g sqrt(I) (needs the stack).  Without pos the
+        rows are the positions of order[]; with pos / dx / dy they are
+        residual_at's entries.  Returns the array, or None when device_ptr
+        names device memory of the caller's that receives it.  The kernels'
+        event time is left in predict_ms.  Read-only, blocking."""
+        if kind not in PREDICT_KINDS:
+            raise ValueError(f"kind {kind!r}: want one of {sorted(PREDICT_KINDS)}")
+        flags = PREDICT_KINDS[kind]
+        if pos is None:
+            if dx is not None or dy is not None:
+                raise ValueError("dx / dy without pos")
+            probes, n = None, len(self.prob.order)
+        else:
+            probes, n = self._probes(pos, np.zeros_like(_i32(pos)) if dx is None else dx,
+                                     np.zeros_like(_i32(pos)) if dy is None else dy)
+        out = None
+        if device_ptr is None:
+            p = self.prob
+            out = np.empty((n, p.n_patch, p.np_, p.np_), np.uint16 if kind == "counts" else np.float32)
+            dst = out.ctypes.data_as(C.c_void_p)
+        else:
+            dst, flags = C.c_void_p(device_ptr), flags | PREDICT_DEVICE
+        ms = C.c_double()
+        _check(_lib.fpm_predict(self._h, probes, n, flags, dst, C.byref(ms)))
+        self.predict_ms = ms.value
+        return out
 
     def set_gains(self, g):
         """fpm_set_gains: the per-image amplitude factor, float32
@@ -720,6 +757,28 @@ def stitch_tiles(tiles, grid, stride, align: str = "none", device: int = 0):
 def normalised_residual(d) -> np.ndarray:
     """Per-patch normalised residual sum_i E / sum_i S of a Solver.residual() dict."""
     return np.asarray(d["err"], np.float64).sum(0) / np.asarray(d["ref"], np.float64).sum(0)
+
+
+def scatter_to_stack(prob: Problem, rows: np.ndarray) -> np.ndarray:
+    """Rows by position of order[] ([n_order][n_patch][Np][Np], what
+    Solver.predict() returns without pos) as a stack [n_stack][n_patch][Np][Np]
+    in upload()'s layout; stack indices not in order[] are zero."""
+    stack = np.zeros((len(prob.x0),) + rows.shape[1:], rows.dtype)
+    stack[np.asarray(prob.order)] = rows
+    return stack
+
+
+def simulate(prob: Problem, objF, pupil, gains=None, device: int = 0) -> np.ndarray:
+    """The uint16 stack [n_stack][n_patch][Np][Np] a camera would record of a
+    known object spectrum and pupil (set_state's layouts) under the LED gains
+    (set_gains' layout; None = all ones): set_state, predict("counts") for
+    every position of order[], scattered to the stack indices.  Images of
+    stack indices order[] does not name are zero."""
+    with Solver(prob, device) as s:
+        s.set_state(objF, pupil)
+        if gains is not None:
+            s.set_gains(gains)
+        return scatter_to_stack(prob, s.predict("counts"))
 
 
 def run_fpm(prob: Problem, stack: np.ndarray, iters: int, device: int = 0):

@@ -40,8 +40,10 @@ extern "C" {
  * FPM_HAS_LED_CALIBRATION = fpm_residual_at, fpm_set_crops, fpm_get_crops;
  * FPM_HAS_LED_GAINS = fpm_set_gains, fpm_get_gains, fpm_moments;
  * FPM_HAS_STATE = fpm_set_state, fpm_download_state_device;
- * FPM_HAS_STITCH = fpm_stitch_tiles, fpm_stitch. */
+ * FPM_HAS_STITCH = fpm_stitch_tiles, fpm_stitch;
+ * FPM_HAS_PREDICT = fpm_predict. */
 #define FPM_ABI_VERSION   6
+#define FPM_HAS_PREDICT 1
 #define FPM_HAS_LED_CALIBRATION 1
 #define FPM_HAS_LED_GAINS 1
 #define FPM_HAS_STATE 1
@@ -301,6 +303,45 @@ int  fpm_get_gains(const fpm_ctx *ctx, float *gain);
  * its own, allocated by its first call. */
 int  fpm_moments(fpm_ctx *ctx, const fpm_probe *probes, int n, double *model, double *cross,
                  double *ref, double *elapsed_ms);
+
+/* The forward model's images of the current state: what each LED should have
+ * produced, psi = ifft2(window * P) with psi as fpm_residual's (scaled 1/Np^2,
+ * no eps), per pixel.  flags = exactly one kind, optionally | FPM_PREDICT_DEVICE:
+ *   AMPLITUDE  float32  |psi|, raw: the gain table does not enter (as fpm_moments)
+ *   COUNTS     uint16   the image the camera would record,
+ *                       sat_u16(rint((|psi| / g)^2)): half to even, saturated at
+ *                       65535, g the image's gain (fpm_set_gains)
+ *   DIFF       float32  |psi| - g sqrt(I), the signed per-pixel mismatch
+ * A gain of 1.0f is bit for bit no gain.
+ *   out [n][n_patch][Np][Np]  pixel (y, x) at y*Np + x whatever layout the
+ *                             context keeps its stack in; host memory, or with
+ *                             FPM_PREDICT_DEVICE memory of the context's device
+ * probes == NULL: the context's own list (n is ignored; n = n_order and row i
+ * is order[i]'s LED, so COUNTS scattered from position i to stack index
+ * order[i] is fpm_upload_stack's layout); otherwise fpm_residual_at's entries,
+ * validation, messages and row order.  n is not limited.
+ * The contract of fpm_residual_at: read-only (spectrum, pupil, maxima,
+ * objCrop, stack, gains, crops, fpm_timing and fpm_clock are left bit for
+ * bit), blocking, deterministic (an entry's bytes depend on the state and on
+ * that entry alone, not on the batch, FPM_RES_BATCH or its neighbours);
+ * FPM_ERR_INVAL on a capturing stream before anything is enqueued, on a NULL
+ * out, on more than one kind and on an unknown flag bit; FPM_ERR_STATE before
+ * a state exists.  AMPLITUDE and COUNTS need no stack and never read it: they
+ * are legal on a context initialised by fpm_set_state alone (simulation).
+ * DIFF returns FPM_ERR_STATE "no stack uploaded" there.
+ * It runs the residual sweep's kernels and scratch.  With a device out the
+ * kernels store straight into the caller's memory; with a host out each
+ * launch's batch goes through a staging buffer of nl * n_patch * Np^2 4-byte
+ * elements (nl = LEDs per launch), allocated by the first such call and
+ * counted in fpm_info.device_bytes from then on.
+ * elapsed_ms (may be NULL): event to event over the kernels; the staging
+ * copies to the host are outside it. */
+#define FPM_PREDICT_AMPLITUDE 0u
+#define FPM_PREDICT_COUNTS    1u
+#define FPM_PREDICT_DIFF      2u
+#define FPM_PREDICT_DEVICE    4u
+int  fpm_predict(fpm_ctx *ctx, const fpm_probe *probes, int n, uint32_t flags, void *out,
+                 double *elapsed_ms);
 
 /* Wait for all work on the context stream. */
 int  fpm_synchronize(fpm_ctx *ctx);
