@@ -29,6 +29,8 @@ fpm_ctx::~fpm_ctx() {
     if (gfork) (void)hipEventDestroy(gfork);
     for (auto e : res_ev)
         if (e) (void)hipEventDestroy(e);
+    for (auto e : rf_ev)
+        if (e) (void)hipEventDestroy(e);
     if (own_stream) (void)hipStreamDestroy(own_stream);
 }
 

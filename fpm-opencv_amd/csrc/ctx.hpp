@@ -6,6 +6,7 @@
 //   run.cpp       fpm_init, fpm_run, the general path's patch groups and graphs
 //   residual_api.cpp  fpm_residual, fpm_residual_at, fpm_moments, fpm_predict (kernels: residual.hip)
 //   state_api.cpp fpm_set_state, fpm_download_state_device (kernels: state.hip)
+//   refocus_api.cpp fpm_refocus (kernels: refocus.hip; the transform is objCrop's)
 //   stitch_api.cpp fpm_stitch_tiles, fpm_stitch (kernels: stitch.hip; solve: stitch_solve.hpp)
 //   api.cpp       errors, version, info, timing, clock, fpm_runFPM
 // Errors are negative codes plus fpm_last_error(); nothing here ever falls
@@ -155,6 +156,15 @@ struct fpm_ctx {
     bool pred_ready = false;        // cols_pred may take its LDS (allow_large_lds)
     // fpm_set_state's check scratch, allocated by its first call
     fpm::StateCheck *state_chk = nullptr;
+    // fpm_refocus' scratch, allocated by its first call: objF H of one plane
+    // [B][L][L] (centred, fp32 on every context; zero outside the live band), the
+    // zl of one piece of the plane list [kRefocusPiece][B], the sums pass's
+    // partials [B][blocks][3] and the folded sums [3][kRefocusPiece][B], two events
+    static constexpr int kRefocusPiece = 64;
+    float2 *rf_spec = nullptr;
+    double *rf_zl = nullptr, *rf_part = nullptr, *rf_sums = nullptr;
+    hipEvent_t rf_ev[2] = {};
+    bool rf_ready = false;
 
     fpm_ctx() = default;
     fpm_ctx(const fpm_ctx &) = delete;

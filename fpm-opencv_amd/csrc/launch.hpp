@@ -246,6 +246,21 @@ bool stitch_blend_vector(const StitchGeom &g, const float2 *tiles, const float2 
 hipError_t launch_stitch_blend(const StitchGeom &g, const float2 *tiles, const float2 *factors, float2 *field,
                                hipStream_t s);
 
+// ---- fpm_refocus (refocus.hip)
+// The angular-spectrum multiply of one plane: scratch [B][L][L] (centred, fp32)
+// = spec_ld(st, b, .) H(zl[b * zstride]) over the live band of st; nothing
+// outside the band is written.  zl is device memory, zstride 0 (one z for
+// every patch) or 1.
+hipError_t launch_refocus_mul(const DevState &st, const double *zl, int zstride, double fl, float2 *scratch,
+                              hipStream_t s);
+// Row strips (= partials) per patch of the sums pass at this L and margin
+int refocus_sum_blocks(int L, int margin);
+// The focus sums of one plane [B][L][L] over [margin, L - margin)^2: per-block
+// partials [B][blocks][3], then the fold in block order into sum_a[b],
+// sum_a2[b], sum_g[b] (device memory, [B] each)
+hipError_t launch_refocus_sums(const float2 *plane, int B, int L, int margin, double *partials, double *sum_a,
+                               double *sum_a2, double *sum_g, hipStream_t s);
+
 // ---- objCrop (objcrop.hip; kernels: crop256m.hip, crop600.hip, crop360.hip, crop4k.hip, fft_batch.hip)
 // The two launches of a register family, one table row per family file.  Every
 // row kernel takes (spec, out, tw, sy0, sy1, sx0, sx1) and every column kernel

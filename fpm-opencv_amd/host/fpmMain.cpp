@@ -86,6 +86,29 @@
 //                      or float32 |psi| - g sqrt(I), the per-pixel mismatch with
 //                      the measurements (diff); result.json gains "predicted":
 //                      kind, shape, ms
+//   --refocus Z0:DZ:N  digital refocusing of the final state (fpm_refocus): the
+//                      field propagated to the N planes z = Z0 + k DZ by the
+//                      angular-spectrum method, Z0 and DZ in the JSON's length
+//                      unit (the one lambda and pixelSize use).  Every patch picks
+//                      the plane where its focus measure is best, and
+//                      objCrop_focus.npy [patches][Nlarge][Nlarge] holds every
+//                      patch at its own plane.  result.json gains "refocus": z, zl
+//                      (= z / lambda), fl (= lambda / (Nlarge ps)), margin,
+//                      measure, pick, sum_a / sum_a2 / sum_g [N][patches] (the
+//                      sums over the interior the measures are made of), plane
+//                      and z_best [patches], ms.  With --grid, objCrop_field.npy
+//                      is made of the focused tiles in place of objCrop: stitched
+//                      on the device with --overlap (fpm_stitch_tiles), placed
+//                      side by side without; objCrop_tiles.npy stays objCrop
+//   --focus-measure nvar|tamura|grad   normalised variance (default), Tamura
+//                      coefficient or gradient energy of the amplitude
+//   --focus-pick max|min   the best plane has the largest (default) or the
+//                      smallest value: min for phase objects, whose amplitude
+//                      contrast is least in focus
+//   --focus-margin PX  the sums leave out PX pixels along the border, where a
+//                      propagated field wraps around (default 8, at most
+//                      Nlarge/2 - 1)
+//   --write-refocus    also write refocus.npy [N][patches][Nlarge][Nlarge]
 //   --init-pupil FILE.npy  start from this pupil instead of the support disk:
 //                      complex64 [Np][Np] (one pupil for every patch) or
 //                      [patches][Np][Np], centred as pupil.npy / pupils.npy are
@@ -116,6 +139,8 @@
 #include <string>
 #include <utility>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "../../include/fpm_hip.h"
 #include "../../include/fpm_host.h"
@@ -160,7 +185,7 @@ bool write_npy_c64_3d(const std::string &path, const float *data, int n0, int n1
     return fclose(f) == 0;
 }
 
-// predicted.npy: float32 ('<f4') or uint16 ('<u2') [n0][n1][n2][n3]
+// predicted.npy: float32 ('<f4') or uint16 ('<u2') [n0][n1][n2][n3]; refocus.npy: complex64 ('<c8')
 bool write_npy_4d(const std::string &path, const void *data, const char *descr, size_t elem, int n0, int n1, int n2,
                   int n3) {
     FILE *f = fopen(path.c_str(), "wb");
@@ -189,7 +214,13 @@ const char *kUsage =
     "  --init-pupil FILE.npy  --init-objf FILE.npy\n"
     "  --write-predicted amplitude|counts|diff\n"
     "      predicted.npy [used][patches][Np][Np]: the forward model's image of every LED for the\n"
-    "      final state (float32 |psi|, uint16 counts, or float32 |psi| - g sqrt(I))\n";
+    "      final state (float32 |psi|, uint16 counts, or float32 |psi| - g sqrt(I))\n"
+    "  --refocus Z0:DZ:N  --focus-measure nvar|tamura|grad  --focus-pick max|min  --focus-margin PX\n"
+    "  --write-refocus\n"
+    "      the final field propagated to the planes z = Z0 + k DZ (the JSON's length unit); every\n"
+    "      patch at the plane its focus measure picks: objCrop_focus.npy [patches][Nlarge][Nlarge];\n"
+    "      --write-refocus: every plane, refocus.npy [N][patches][Nlarge][Nlarge]; with --grid the\n"
+    "      field is made of the focused tiles (stitched with --overlap, placed side by side without)\n";
 
 // A .npy file of little-endian complex64 in C order, format version 1.0 or
 // 2.0: its shape and its values as (re, im) pairs.  The header's shape must
@@ -337,6 +368,11 @@ int main(int argc, char **argv) {
     std::string stitch_align;  // --stitch-align none|phase|complex
     bool write_tiles = false;  // --write-tiles: objCrop_tiles.npy [B][L][L] as well
     std::string predicted;     // --write-predicted amplitude|counts|diff: predicted.npy of the final state
+    int rf_n = 0;              // --refocus Z0:DZ:N: planes z = Z0 + k DZ (0: not given)
+    double rf_z0 = 0, rf_dz = 0;
+    std::string focus_measure = "nvar", focus_pick = "max";  // --focus-measure, --focus-pick
+    int focus_margin = -1;     // --focus-margin PX (-1: the default)
+    bool write_refocus = false, focus_opt = false;  // --write-refocus; some --focus-* option was given
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--out" && i + 1 < argc) out_dir = argv[++i];
@@ -370,6 +406,41 @@ int main(int argc, char **argv) {
                 return 2;
             }
         }
+        else if (a == "--refocus" && i + 1 < argc) {
+            char tail = 0;
+            if (sscanf(argv[++i], "%lf:%lf:%d%c", &rf_z0, &rf_dz, &rf_n, &tail) != 3 || !std::isfinite(rf_z0) ||
+                !std::isfinite(rf_dz) || rf_n < 1 || rf_n > 4096) {
+                std::cerr << "--refocus wants Z0:DZ:N, e.g. -20:5:9 (N planes from 1 to 4096)" << std::endl;
+                return 2;
+            }
+        }
+        else if (a == "--focus-measure" && i + 1 < argc) {
+            focus_measure = argv[++i];
+            focus_opt = true;
+            if (focus_measure != "nvar" && focus_measure != "tamura" && focus_measure != "grad") {
+                std::cerr << "--focus-measure wants nvar, tamura or grad" << std::endl;
+                return 2;
+            }
+        }
+        else if (a == "--focus-pick" && i + 1 < argc) {
+            focus_pick = argv[++i];
+            focus_opt = true;
+            if (focus_pick != "max" && focus_pick != "min") {
+                std::cerr << "--focus-pick wants max or min" << std::endl;
+                return 2;
+            }
+        }
+        else if (a == "--focus-margin" && i + 1 < argc) {
+            char *end = nullptr;
+            const long v = strtol(argv[++i], &end, 10);
+            focus_opt = true;
+            if (end == argv[i] || *end || v < 0 || v > (1 << 20)) {
+                std::cerr << "--focus-margin wants a number of pixels >= 0" << std::endl;
+                return 2;
+            }
+            focus_margin = (int)v;
+        }
+        else if (a == "--write-refocus") write_refocus = true;
         else if (a == "--calibrate-gains") want_gains = true;
         else if (a == "--calibrate-leds" && i + 1 < argc) {
             cal_radius = atoi(argv[++i]);
@@ -394,6 +465,10 @@ int main(int argc, char **argv) {
     }
     if (!stitch_align.empty() && overlap < 0) {
         std::cerr << "--stitch-align needs --overlap: without it the tiles share no pixels to align on" << std::endl;
+        return 2;
+    }
+    if ((write_refocus || focus_opt) && rf_n < 1) {
+        std::cerr << "--write-refocus and --focus-* need --refocus Z0:DZ:N: they describe its planes" << std::endl;
         return 2;
     }
     // use_cpu.sh / use_gpu.sh select the OpenCL device (use_gpu.sh:1)
@@ -424,6 +499,18 @@ int main(int argc, char **argv) {
         std::cerr << "--overlap " << overlap << " exceeds Np/2 = " << cfg.np / 2
                   << ": a pixel may lie in at most two patches per axis" << std::endl;
         return 2;
+    }
+    if (rf_n > 0) {
+        if (focus_margin < 0) focus_margin = std::min(8, (cfg.nlarge - 2) / 2);
+        if (2 * focus_margin > cfg.nlarge - 2) {
+            std::cerr << "--focus-margin " << focus_margin << " leaves no interior: at most " << (cfg.nlarge - 2) / 2
+                      << " for Nlarge " << cfg.nlarge << std::endl;
+            return 2;
+        }
+        if (!(cfg.lambda > 0) || !(cfg.ps > 0)) {
+            std::cerr << "--refocus needs lambda and pixelSize > 0 in the dataset JSON" << std::endl;
+            return 2;
+        }
     }
     if (overlap > 0 && stitch_align.empty()) stitch_align = "phase";
     if (overlap == 0 && stitch_align.empty()) stitch_align = "none";
@@ -704,13 +791,88 @@ int main(int argc, char **argv) {
     std::vector<float> st_field;
     std::vector<double> st_factors;
     double st_ms = 0;
+    const fpm_stitch_grid sg = {gy, gx, L, st_stride, st_stride};
+    const uint32_t sflags = stitch_align == "phase"     ? FPM_STITCH_ALIGN_PHASE
+                            : stitch_align == "complex" ? FPM_STITCH_ALIGN_COMPLEX
+                                                        : 0u;
     if (blend) {
         st_field.resize((size_t)st_h * st_w * 2);
         st_factors.resize((size_t)B * 2);
-        const fpm_stitch_grid sg = {gy, gx, L, st_stride, st_stride};
-        const uint32_t sflags = stitch_align == "phase"     ? FPM_STITCH_ALIGN_PHASE
-                                : stitch_align == "complex" ? FPM_STITCH_ALIGN_COMPLEX
-                                                            : 0u;
+    }
+    // --refocus: the sweep (sums, and every plane with --write-refocus), the
+    // host's choice of a plane per patch, then every patch at its own z from one
+    // per-patch call.  With --overlap that call stores into device memory and the
+    // focused tiles are stitched where they lie (fpm_stitch_tiles).
+    const size_t tile_f = (size_t)L * L * 2;
+    std::vector<double> rf_z(rf_n), rf_zl(rf_n), rf_sa, rf_sa2, rf_sg, rf_zbest(B);
+    std::vector<int> rf_plane(B, 0);
+    std::vector<float> rf_all, rf_focus;
+    const double rf_fl = rf_n > 0 ? (double)cfg.lambda / ((double)L * (double)cfg.ps) : 0.0;
+    double rf_ms = 0;
+    if (rf_n > 0) {
+        const size_t nb = (size_t)rf_n * B;
+        for (int k = 0; k < rf_n; ++k) {
+            rf_z[k] = rf_z0 + k * rf_dz;
+            rf_zl[k] = rf_z[k] / (double)cfg.lambda;
+        }
+        rf_sa.resize(nb);
+        rf_sa2.resize(nb);
+        rf_sg.resize(nb);
+        if (write_refocus) rf_all.resize(nb * tile_f);
+        double ms = 0;
+        if ((rc = fpm_refocus(ctx, rf_zl.data(), rf_n, rf_fl, focus_margin, 0u, write_refocus ? rf_all.data() : nullptr,
+                              rf_sa.data(), rf_sa2.data(), rf_sg.data(), &ms))) {
+            std::cerr << "fpm: " << fpm_last_error() << std::endl;
+            return 1;
+        }
+        rf_ms += ms;
+        // N = |R|, m = sum_a / N, v = sum_a2 / N - m^2: v / m^2, sqrt(sqrt(v) / m), sum_g / sum_a2
+        const double N = (double)(L - 2 * focus_margin) * (L - 2 * focus_margin);
+        auto measure = [&](size_t k) {
+            const double m = rf_sa[k] / N, v = std::max(rf_sa2[k] / N - m * m, 0.0);
+            return focus_measure == "nvar" ? v / (m * m) : focus_measure == "tamura" ? std::sqrt(std::sqrt(v) / m)
+                                                                                     : rf_sg[k] / rf_sa2[k];
+        };
+        std::vector<double> zlb(B);
+        for (int b = 0; b < B; ++b) {
+            for (int k = 1; k < rf_n; ++k) {  // the first of equal values
+                const double v = measure((size_t)k * B + b), best = measure((size_t)rf_plane[b] * B + b);
+                if (focus_pick == "max" ? v > best : v < best) rf_plane[b] = k;
+            }
+            rf_zbest[b] = rf_z[rf_plane[b]];
+            zlb[b] = rf_zl[rf_plane[b]];
+        }
+        rf_focus.resize((size_t)B * tile_f);
+        if (!blend) {
+            rc = fpm_refocus(ctx, zlb.data(), 1, rf_fl, focus_margin, FPM_REFOCUS_Z_PER_PATCH, rf_focus.data(), nullptr,
+                             nullptr, nullptr, &ms);
+        } else {
+            struct Dev {
+                void *p = nullptr;
+                ~Dev() { (void)hipFree(p); }
+            } tiles, field;
+            const size_t tb = (size_t)B * tile_f * sizeof(float), fb = st_field.size() * sizeof(float);
+            if (hipSetDevice(device) != hipSuccess || hipMalloc(&tiles.p, tb) != hipSuccess || hipMalloc(&field.p, fb) != hipSuccess) {
+                std::cerr << "--refocus: no device memory for the focused tiles and the field" << std::endl;
+                return 1;
+            }
+            rc = fpm_refocus(ctx, zlb.data(), 1, rf_fl, focus_margin, FPM_REFOCUS_Z_PER_PATCH | FPM_REFOCUS_DEVICE,
+                             (float *)tiles.p, nullptr, nullptr, nullptr, &ms);
+            if (!rc)
+                rc = fpm_stitch_tiles(device, (const float *)tiles.p, &sg, sflags | FPM_STITCH_DEVICE, (float *)field.p,
+                                      st_factors.data(), nullptr, &st_ms);
+            if (!rc && (hipMemcpy(rf_focus.data(), tiles.p, tb, hipMemcpyDeviceToHost) != hipSuccess ||
+                        hipMemcpy(st_field.data(), field.p, fb, hipMemcpyDeviceToHost) != hipSuccess)) {
+                std::cerr << "--refocus: copying the focused tiles and the field back failed" << std::endl;
+                return 1;
+            }
+        }
+        if (rc) {
+            std::cerr << "fpm: " << fpm_last_error() << std::endl;
+            return 1;
+        }
+        rf_ms += ms;
+    } else if (blend) {
         if ((rc = fpm_stitch(ctx, &sg, sflags, st_field.data(), st_factors.data(), &st_ms))) {
             std::cerr << "fpm: " << fpm_last_error() << std::endl;
             return 1;
@@ -743,14 +905,16 @@ int main(int argc, char **argv) {
              write_npy_c64_3d(out_dir + "/pupils.npy", pupil.data(), B, np, np);
     } else {
         // stitch: tile b = (i, j) lands at rows i L, columns j L (tiles do not
-        // overlap); row-wise copies of L complex values
+        // overlap); row-wise copies of L complex values.  With
+        // --refocus the tiles placed are the focused ones
+        const std::vector<float> &tiles = rf_n > 0 ? rf_focus : objCrop;
         const size_t FW = (size_t)gx * L;
         std::vector<float> field((size_t)gy * L * FW * 2);
         for (int b = 0; b < B; ++b) {
             const int i = b / gx, j = b % gx;
             for (int y = 0; y < L; ++y)
                 std::memcpy(&field[(((size_t)i * L + y) * FW + (size_t)j * L) * 2],
-                            &objCrop[(((size_t)b * L + y) * L) * 2], (size_t)L * 2 * sizeof(float));
+                            &tiles[(((size_t)b * L + y) * L) * 2], (size_t)L * 2 * sizeof(float));
         }
         ok = write_npy_c64(out_dir + "/objCrop_field.npy", field.data(), gy * L, gx * L) &&
              write_npy_c64_3d(out_dir + "/pupils.npy", pupil.data(), B, np, np);
@@ -759,6 +923,8 @@ int main(int argc, char **argv) {
     if (ok && !predicted.empty())
         ok = write_npy_4d(out_dir + "/predicted.npy", pred.data(), predicted == "counts" ? "<u2" : "<f4",
                           predicted == "counts" ? 2 : 4, used, B, np, np);
+    if (ok && rf_n > 0) ok = write_npy_c64_3d(out_dir + "/objCrop_focus.npy", rf_focus.data(), B, L, L);
+    if (ok && write_refocus) ok = write_npy_4d(out_dir + "/refocus.npy", rf_all.data(), "<c8", 8, rf_n, B, L, L);
     if (ok) {  // JSON sidecar describing the arrays (replaces the reference's display windows)
         FILE *f = fopen((out_dir + "/result.json").c_str(), "w");
         ok = f != nullptr;
@@ -846,6 +1012,35 @@ int main(int argc, char **argv) {
             if (!predicted.empty())
                 fprintf(f, "  \"predicted\": {\"kind\": \"%s\", \"shape\": [%d, %d, %d, %d], \"ms\": %.6f},\n",
                         predicted.c_str(), used, B, np, np, pred_ms);
+            if (rf_n > 0) {
+                auto put_list = [&](const char *name, const std::vector<double> &v) {
+                    fprintf(f, "\"%s\": [", name);
+                    for (size_t i = 0; i < v.size(); ++i) fprintf(f, "%s%.17g", i ? ", " : "", v[i]);
+                    fprintf(f, "], ");
+                };
+                auto put_table = [&](const char *name, const std::vector<double> &v) {  // [N][patches]
+                    fprintf(f, "\"%s\": [", name);
+                    for (int k = 0; k < rf_n; ++k) {
+                        fprintf(f, "%s[", k ? ", " : "");
+                        for (int b = 0; b < B; ++b) fprintf(f, "%s%.17g", b ? ", " : "", v[(size_t)k * B + b]);
+                        fprintf(f, "]");
+                    }
+                    fprintf(f, "], ");
+                };
+                fprintf(f, "  \"refocus\": {");
+                put_list("z", rf_z);
+                put_list("zl", rf_zl);
+                fprintf(f, "\"fl\": %.17g, \"margin\": %d, \"measure\": \"%s\", \"pick\": \"%s\", ", rf_fl,
+                        focus_margin, focus_measure.c_str(), focus_pick.c_str());
+                put_table("sum_a", rf_sa);
+                put_table("sum_a2", rf_sa2);
+                put_table("sum_g", rf_sg);
+                fprintf(f, "\"plane\": [");
+                for (int b = 0; b < B; ++b) fprintf(f, "%s%d", b ? ", " : "", rf_plane[b]);
+                fprintf(f, "], ");
+                put_list("z_best", rf_zbest);
+                fprintf(f, "\"ms\": %.6f},\n", rf_ms);
+            }
             if (blend) {  // factors in row-major patch order, (re, im)
                 fprintf(f, "  \"stitch\": {\"overlap\": %d, \"stride\": %d, \"align\": \"%s\", \"field\": [%d, %d], "
                            "\"factors\": [", overlap, st_stride, stitch_align.c_str(), st_h, st_w);
@@ -865,11 +1060,12 @@ int main(int argc, char **argv) {
                 if (blend)
                     fprintf(f, "    \"objCrop_field.npy\": \"complex64 [(gy-1)*stride+Nlarge][(gx-1)*stride+Nlarge], "
                                "the patches' objCrop tiles at rows i*stride, columns j*stride times their stitch "
-                               "factors, feathered over the overlaps (fpm_stitch)\",\n");
+                               "factors, feathered over the overlaps (fpm_stitch)%s\",\n",
+                            rf_n > 0 ? "; the tiles are objCrop_focus.npy's, every patch at its plane of best focus" : "");
                 else
                     fprintf(f, "    \"objCrop_field.npy\": \"complex64 [gy*Nlarge][gx*Nlarge], patch (i, j) = "
                                "IDFT(objF)/Nlarge^2 of the crop at (cropX + j*Np, cropY + i*Np) at rows i*Nlarge, "
-                               "columns j*Nlarge\",\n");
+                               "columns j*Nlarge%s\",\n", rf_n > 0 ? ", every patch at its plane of best focus" : "");
                 fprintf(f, "    \"pupils.npy\": \"complex64 [gy*gx][Np][Np], centred pupil per patch, row-major "
                            "patch order\"\n  }\n}\n");
             } else {

@@ -46,6 +46,9 @@ STITCH_ALIGN = {"none": 0, "phase": STITCH_ALIGN_PHASE, "complex": STITCH_ALIGN_
 # fpm_predict flags (fpm_hip.h FPM_PREDICT_*): one kind, optionally | PREDICT_DEVICE
 PREDICT_AMPLITUDE, PREDICT_COUNTS, PREDICT_DIFF, PREDICT_DEVICE = 0, 1, 2, 4
 PREDICT_KINDS = {"amplitude": PREDICT_AMPLITUDE, "counts": PREDICT_COUNTS, "diff": PREDICT_DIFF}
+# fpm_refocus flags (fpm_hip.h FPM_REFOCUS_*)
+REFOCUS_DEVICE = 1          # planes is a device pointer on the context's device
+REFOCUS_Z_PER_PATCH = 2     # zl is [nz][n_patch]
 
 # fpm_info.fused_kernel: the LED-update kernel of the context (fpm_hip.h FPM_KERNEL_*)
 KERNEL_GENERAL, KERNEL_FUSED_NP256, KERNEL_FUSED_NP200, KERNEL_FUSED_SMALL, KERNEL_FUSED_NP256_DIST = 0, 1, 2, 3, 4
@@ -63,7 +66,7 @@ HIP_SYMBOLS = (
     "fpm_upload_frames", "fpm_download_stack", "fpm_get_info_sized", "fpm_abi_version",
     "fpm_get_clock", "fpm_residual", "fpm_residual_at", "fpm_set_crops", "fpm_get_crops",
     "fpm_set_gains", "fpm_get_gains", "fpm_moments", "fpm_set_state", "fpm_download_state_device",
-    "fpm_stitch_tiles", "fpm_stitch", "fpm_predict",
+    "fpm_stitch_tiles", "fpm_stitch", "fpm_predict", "fpm_refocus",
 )
 # test-only entry points (include/fpm_hip_debug.h)
 HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan",
@@ -204,6 +207,8 @@ def load_library(path: str = HIP_LIB):
         "fpm_get_gains": (C.c_int, [vp, f32p]),
         "fpm_moments": (C.c_int, [vp, C.POINTER(fpm_probe), C.c_int] + [C.POINTER(C.c_double)] * 4),
         "fpm_predict": (C.c_int, [vp, C.POINTER(fpm_probe), C.c_int, C.c_uint32, vp, C.POINTER(C.c_double)]),
+        "fpm_refocus": (C.c_int, [vp, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_int, C.c_uint32, vp]
+                        + [C.POINTER(C.c_double)] * 4),
         "fpm_set_state": (C.c_int, [vp, vp, vp, C.c_uint32]),
         "fpm_download_state_device": (C.c_int, [vp, vp, vp]),
         "fpm_stitch_tiles": (C.c_int, [C.c_int, vp, C.POINTER(fpm_stitch_grid), C.c_uint32, vp,
@@ -453,6 +458,43 @@ class Solver:
         _check(_lib.fpm_predict(self._h, probes, n, flags, dst, C.byref(ms)))
         self.predict_ms = ms.value
         return out
+
+    def refocus(self, zl, fl: float, margin: int = 0, planes: bool = True, device_ptr: int | None = None,
+                sums: bool = True):
+        """fpm_refocus: the field of the current state propagated to the planes
+        zl = z / lambda (1-D [nz]: one z for every patch; 2-D [nz][n_patch]: a z
+        per patch) by the angular-spectrum method, fl = lambda / (L ps) the
+        normalised frequency of one spectrum bin (focus.bin_frequency).  Returns
+        (planes, sums): planes complex64 [nz][n_patch][L][L], or None when
+        planes is False (the autofocus sweep: nothing but the sums leaves the
+        device) or device_ptr names device memory of the caller's that receives
+        them; sums = dict(sum_a, sum_a2, sum_g), float64 [nz][n_patch] over the
+        interior [margin, L - margin)^2 (focus.measures makes the focus measures
+        of them), or None when sums is False.  The kernels' event time is left
+        in refocus_ms.  Read-only, blocking."""
+        p = self.prob
+        z = np.ascontiguousarray(zl, dtype=np.float64)
+        flags = 0
+        if z.ndim == 2:
+            if z.shape[1] != p.n_patch:
+                raise ValueError(f"zl shape {z.shape}: want [nz][{p.n_patch}]")
+            flags |= REFOCUS_Z_PER_PATCH
+        elif z.ndim != 1:
+            raise ValueError(f"zl shape {z.shape}: want [nz] or [nz][n_patch]")
+        nz = z.shape[0]
+        out, dst = None, None
+        if device_ptr is not None:
+            dst, flags = C.c_void_p(device_ptr), flags | REFOCUS_DEVICE
+        elif planes:
+            out = np.empty((nz, p.n_patch, p.L, p.L), np.complex64)
+            dst = out.ctypes.data_as(C.c_void_p)
+        dp = C.POINTER(C.c_double)
+        s = [np.empty((nz, p.n_patch), np.float64) for _ in range(3)] if sums else None
+        ms = C.c_double()
+        _check(_lib.fpm_refocus(self._h, z.ctypes.data_as(dp), nz, float(fl), int(margin), flags, dst,
+                                *((a.ctypes.data_as(dp) for a in s) if sums else (None, None, None)), C.byref(ms)))
+        self.refocus_ms = ms.value
+        return out, (dict(sum_a=s[0], sum_a2=s[1], sum_g=s[2]) if sums else None)
 
     def set_gains(self, g):
         """fpm_set_gains: the per-image amplitude factor, float32

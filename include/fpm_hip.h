@@ -41,9 +41,11 @@ extern "C" {
  * FPM_HAS_LED_GAINS = fpm_set_gains, fpm_get_gains, fpm_moments;
  * FPM_HAS_STATE = fpm_set_state, fpm_download_state_device;
  * FPM_HAS_STITCH = fpm_stitch_tiles, fpm_stitch;
- * FPM_HAS_PREDICT = fpm_predict. */
+ * FPM_HAS_PREDICT = fpm_predict;
+ * FPM_HAS_REFOCUS = fpm_refocus. */
 #define FPM_ABI_VERSION   6
 #define FPM_HAS_PREDICT 1
+#define FPM_HAS_REFOCUS 1
 #define FPM_HAS_LED_CALIBRATION 1
 #define FPM_HAS_LED_GAINS 1
 #define FPM_HAS_STATE 1
@@ -342,6 +344,67 @@ int  fpm_moments(fpm_ctx *ctx, const fpm_probe *probes, int n, double *model, do
 #define FPM_PREDICT_DEVICE    4u
 int  fpm_predict(fpm_ctx *ctx, const fpm_probe *probes, int n, uint32_t flags, void *out,
                  double *elapsed_ms);
+
+/* Digital refocusing: the recovered field propagated to other z planes by the
+ * angular-spectrum method, and the sums a focus measure is made of, without
+ * the spectrum leaving the device.  The arguments are dimensionless, as
+ * fpm_problem is:
+ *   zl [nz]   z / lambda, the signed distance in wavelengths; with
+ *             FPM_REFOCUS_Z_PER_PATCH [nz][n_patch], every patch its own
+ *   fl        lambda / (L ps), the normalised frequency of one spectrum bin
+ *             (ps the high-resolution pixel size, fpm_host's ps)
+ * Plane.  With objF as fpm_download returns it (un-centred) and signed bin
+ * indices ky, kx in [-L/2, L/2):
+ *   s   = fl^2 (kx^2 + ky^2)
+ *   H   = exp(+i 2 pi zl sqrt(1 - s)) for s <= 1, 0 for s > 1 (evanescent)
+ *   u_z = IDFT2(objF H) / L^2        (objCrop's transform and scale)
+ * The phase is taken in double: c = zl sqrt(1 - s) is reduced to c - rint(c)
+ * and the fp32 sine and cosine of that fraction of a turn are used, so H is
+ * correct to fp32 rounding for every accepted zl.  A plane whose zl entries are
+ * all exactly 0 is the transform of the stored spectrum itself: the bits of
+ * fpm_download's objCrop (its evanescent bins included).
+ *   planes [nz][n_patch][L][L][2]  host memory, or with FPM_REFOCUS_DEVICE
+ *                                  memory of the context's device, clear of
+ *                                  the context's own buffers; may be NULL
+ * Focus sums, per plane and patch over the interior R = [margin, L - margin)^2
+ * (a propagated field wraps around its border), a the fp32 magnitude of u_z:
+ *   sum_a  [nz][n_patch]  sum_R a
+ *   sum_a2 [nz][n_patch]  sum_R a^2
+ *   sum_g  [nz][n_patch]  sum (a(y,x+1) - a(y,x))^2 + sum (a(y+1,x) - a(y,x))^2
+ *                         over the pairs that lie wholly in R
+ * Differences and squares are formed and accumulated in double in a fixed
+ * order (per-block partials, then a fold; no floating-point atomics).  Any of
+ * the three may be NULL.  With N = |R|, m = sum_a / N, v = sum_a2 / N - m^2:
+ * normalised variance v / m^2, Tamura coefficient sqrt(sqrt(v) / m), gradient
+ * energy sum_g / sum_a2; which one suits a sample is the caller's choice.
+ * Accuracy: a carries fp32 rounding (relative e of about 1e-7), so sum_a and
+ * sum_a2 are good to that, but sum_g is a sum of differences: its relative
+ * error is about 2 e sqrt(sum_a2 / sum_g), which grows without bound as the
+ * interior becomes flat (1e-6 at sum_g / sum_a2 = 1e-2, 1e-5 at 1e-4).
+ * With planes == NULL only the sums are produced (the autofocus sweep: nothing
+ * leaves the device but 3 nz n_patch doubles).
+ * The contract of fpm_predict: read-only (spectrum, pupil, maxima, stack,
+ * gains, crops, fpm_timing and fpm_clock are left bit for bit; what
+ * fpm_download returns afterwards is unchanged: the objCrop buffer serves as
+ * the plane staging and is recomputed lazily, as after fpm_set_state),
+ * blocking, deterministic: a plane's bytes and sums depend on the state and on
+ * that plane's zl alone, not on its neighbours in the list or on nz.
+ * FPM_ERR_STATE before a state exists (a context that only had fpm_set_state is
+ * legal); FPM_ERR_INVAL on a capturing stream before anything is enqueued, and,
+ * naming the argument, on a NULL zl, nz < 1, a zl that is not finite or with
+ * |zl| > 1e6 (naming its index; beyond that the double reduction no longer
+ * gives an fp32-exact phase), fl not finite or <= 0, margin < 0 or
+ * 2 margin > L - 2, an unknown flag bit, every output NULL.
+ * With a device `planes` the transform stores straight into the caller's
+ * memory; with a host pointer each plane is copied out after its kernels.
+ * elapsed_ms (may be NULL): event to event over the kernels; the host copies
+ * are outside it.  The first call allocates the scratch ([n_patch][L][L] fp32
+ * complex for objF H, the partial and folded sums; counted in
+ * fpm_info.device_bytes from then on). */
+#define FPM_REFOCUS_DEVICE      1u  /* planes is device memory on the context's device */
+#define FPM_REFOCUS_Z_PER_PATCH 2u  /* zl is [nz][n_patch] instead of [nz] */
+int  fpm_refocus(fpm_ctx *ctx, const double *zl, int nz, double fl, int margin, uint32_t flags,
+                 float *planes, double *sum_a, double *sum_a2, double *sum_g, double *elapsed_ms);
 
 /* Wait for all work on the context stream. */
 int  fpm_synchronize(fpm_ctx *ctx);
