@@ -28,10 +28,21 @@ def initial_state(stack, order, np_, L, radius, init_pos=1, dtype=np.complex128)
 
 
 def iterate(objF, pupil, stack, order, x0, y0, np_, L, radius, delta1, delta2, iters=1,
-            eps=float(np.float32(1e-10)), all_channels=True, dtype=np.complex128):
+            eps=float(np.float32(1e-10)), all_channels=True, dtype=np.complex128, record=None, objf_max=None,
+            objcrop=True):
     """`iters` passes over order[] (:345-482) from the state (objF un-centred,
     pupil centred, as downloaded) with the crop table (x0, y0).  Returns
-    dict(objF, objCrop, pupil, support) like run_fpm."""
+    dict(objF, objCrop, pupil, support) like run_fpm.
+
+    The three last arguments leave the results bit for bit as they are without
+    them (tests/test_probe.py).  `record`: a list that receives one dict per
+    LED step: led, psi_min = min |psi + eps cs| (the divisor of the amplitude
+    replacement), psi_max = max |psi|, objf_max and objf_argmax = max|objF|
+    after the step's object update and its (y, x) in the CENTRED spectrum.
+    `objf_max(objF_c, led)`
+    replaces max|objF| in the pupil update's coefficient (objF_c: the centred
+    spectrum after the object update): what a kernel with a wrong maximum would
+    compute.  objcrop=False skips the final L x L transform (objCrop is None)."""
     ct = np.dtype(dtype)
     rt = np.float64 if ct == np.complex128 else np.float32
     stack = np.asarray(stack)
@@ -50,6 +61,7 @@ def iterate(objF, pupil, stack, order, x0, y0, np_, L, radius, delta1, delta2, i
             object_amp = np.sqrt(stack[led].astype(rt))                 # :378-387
             tmp1 = objcropP + eps * cs                                  # :390
             tmp3 = np.abs(tmp1)                                         # :391
+            psi = (float(tmp3.min()), float(np.abs(objcropP).max())) if record is not None else None
             tmp1 = objcropP / tmp3                                      # :392
             tmp3 = tmp1 * object_amp                                    # :393
             objfup = np.fft.fft2(tmp3).astype(ct, copy=False)           # :394
@@ -62,8 +74,14 @@ def iterate(objF, pupil, stack, order, x0, y0, np_, L, radius, delta1, delta2, i
             objF = fftshift2(objF_c)                                    # :447
             objfcrop_abs = np.abs(objfcrop)
             objf_abs_max = np.abs(objF).max()                           # :460,467
+            if record is not None:
+                m = np.abs(fftshift2(objF))
+                record.append(dict(led=led, psi_min=psi[0], psi_max=psi[1], objf_max=float(objf_abs_max),
+                                   objf_argmax=tuple(int(v) for v in np.unravel_index(int(np.argmax(m)), m.shape))))
+            if objf_max is not None:
+                objf_abs_max = rt(objf_max(fftshift2(objF), led))
             numerator = (objfup - objfcropP) * (objfcrop_abs * np.conj(objfcrop))
             denom = (objfcrop_abs * objfcrop_abs + delta1 * cs) * objf_abs_max  # :469-470
             pupil = pupil + (numerator / denom) * support               # :471-475
-    return dict(objF=objF, objCrop=np.fft.ifft2(objF).astype(ct, copy=False), pupil=fftshift2(pupil),
-                support=support)
+    return dict(objF=objF, objCrop=np.fft.ifft2(objF).astype(ct, copy=False) if objcrop else None,
+                pupil=fftshift2(pupil), support=support)
