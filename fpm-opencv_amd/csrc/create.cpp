@@ -214,8 +214,10 @@ int lds_fits(const fpm_ctx *c, const char *what, const StepKernel &k, size_t lds
 // the sweep's LDS pair (the register pair's LDS does not grow with the problem)
 int residual_lds_fits(const fpm_ctx *c, size_t lds_limit) {
     if (c->rplan.kind != ResidualPlan::Lds) return FPM_OK;
-    const int rc = lds_fits(c, "residual row", c->rplan.rows, lds_limit);
-    return rc ? rc : lds_fits(c, "residual column", c->rplan.cols, lds_limit);
+    int rc = lds_fits(c, "residual row", c->rplan.rows, lds_limit);
+    if (!rc) rc = lds_fits(c, "residual column", c->rplan.cols, lds_limit);
+    if (!rc) rc = lds_fits(c, "gradient column", c->rplan.cols_grad, lds_limit);
+    return rc ? rc : lds_fits(c, "gradient row", c->rplan.grad_rows, lds_limit);
 }
 
 // objCrop's launches: only the batched transform's LDS grows with the problem
@@ -434,7 +436,8 @@ const char *plan_difference(const fpm_ctx *a, const fpm_ctx *b) {
     const ResidualPlan &p = a->rplan, &q = b->rplan;
     if (p.kind != q.kind || p.nblk != q.nblk || p.nl != q.nl || p.t_led != q.t_led || !same_kernel(p.rows, q.rows) ||
         !same_kernel(p.cols, q.cols) || !same_kernel(p.cols_gain, q.cols_gain) || !same_kernel(p.cols_mom, q.cols_mom) ||
-        !same_kernel(p.cols_pred, q.cols_pred))
+        !same_kernel(p.cols_pred, q.cols_pred) || !same_kernel(p.cols_grad, q.cols_grad) ||
+        !same_kernel(p.grad_rows, q.grad_rows))
         return "the residual sweep's plan";
     for (int g = 0; !a->fused() && g < a->ngroups; ++g) {
         const GeneralPlan &u = a->gplan[g], &v = b->gplan[g];
@@ -695,7 +698,8 @@ int fpm_debug_get_ladder(const fpm_ctx *c, int residual, fpm_ladder *out) {
         HIP_TRY(hipSetDevice(c->device));
         int rc = static_lds_matches(p.rows);
         if (rc || (rc = static_lds_matches(p.cols)) || (rc = static_lds_matches(p.cols_gain)) ||
-            (rc = static_lds_matches(p.cols_mom)) || (rc = static_lds_matches(p.cols_pred)))
+            (rc = static_lds_matches(p.cols_mom)) || (rc = static_lds_matches(p.cols_pred)) ||
+            (rc = static_lds_matches(p.cols_grad)) || (rc = static_lds_matches(p.grad_rows)))
             return rc;
         out->rows = ladder_kernel(p.rows, p.ladder.row_e, 0, p.rows.lds_static);
         out->cols = ladder_kernel(p.cols, p.ladder.col_e, p.ladder.cw, p.cols.lds_static);

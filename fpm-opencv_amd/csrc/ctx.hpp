@@ -5,6 +5,7 @@
 //   transfer.cpp  the stack uploads and the downloads
 //   run.cpp       fpm_init, fpm_run, the general path's patch groups and graphs
 //   residual_api.cpp  fpm_residual, fpm_residual_at, fpm_moments, fpm_predict (kernels: residual.hip)
+//   gradient_api.cpp  fpm_gradient (kernels: gradient.hip and the sweep's column kernels)
 //   state_api.cpp fpm_set_state, fpm_download_state_device (kernels: state.hip)
 //   refocus_api.cpp fpm_refocus (kernels: refocus.hip; the transform is objCrop's)
 //   stitch_api.cpp fpm_stitch_tiles, fpm_stitch (kernels: stitch.hip; solve: stitch_solve.hpp)
@@ -154,6 +155,11 @@ struct fpm_ctx {
     // elements), allocated by its first call with a host output
     uint32_t *pred_stage = nullptr;
     bool pred_ready = false;        // cols_pred may take its LDS (allow_large_lds)
+    // fpm_gradient's own: R of one batch [nl][B][nb][nb] by its first call, and the
+    // device copies of host outputs ([B][L][L], [B][Np][Np]) by the first call that
+    // asks for each
+    float2 *grad_R = nullptr, *grad_obj = nullptr, *grad_pupil = nullptr;
+    bool grad_ready = false;        // cols_grad / grad_rows may take their LDS (allow_large_lds)
     // fpm_set_state's check scratch, allocated by its first call
     fpm::StateCheck *state_chk = nullptr;
     // fpm_refocus' scratch, allocated by its first call: objF H of one plane
@@ -204,6 +210,16 @@ int dalloc(fpm_ctx *c, T **p, size_t count, bool zero) {
 // blocking entry points (event waits, read-backs) never run inside a capture:
 // FPM_ERR_INVAL for `what` on a capturing stream, before anything is enqueued (run.cpp)
 int refuse_capture(const fpm_ctx *c, const char *what);
+
+// the sweep's entry checks, probe resolution and scratch (residual_api.cpp), for
+// the entry points in other files that run its kernels (gradient_api.cpp):
+// what every call checks before anything is enqueued (a context, a state, a
+// stack, no capture); the probes as entries, validated, messages under `what`;
+// the scratch and events of the first call
+int sweep_admit(fpm_ctx *c, const char *what);
+int sweep_resolve_probes(const fpm_ctx *c, const char *what, const fpm_probe *probes, int n,
+                         std::vector<ResEntry> &ent);
+int sweep_ensure_scratch(fpm_ctx *c);
 
 // the objCrop IDFT of the current spectrum (run.cpp); ensure: only when the
 // buffer does not hold it yet

@@ -129,6 +129,22 @@ __global__ void __launch_bounds__(256) k_colpass(DevState st, A a, FftPlan pl,
             }
             pred_store(a, o + (size_t)y * np, pred_value(a, res[y], inv_n2, rg_led, iv));
         }
+    } else if constexpr (kIsGrad<A>) {
+        // fpm_gradient: the sums and rho in one walk (the stack where it lies),
+        // then the step's tail: forward column transform, box rows back to T
+        const int g = st.meas_g, npg = g ? np / g : 1;
+        const float rg = 1.0f / (float)(g ? g : 1);
+        ResAcc<A> acc(rg_led);
+        for (int y = threadIdx.x; y < np; y += blockDim.x) {
+            const int m = udiv(y, g ? g : 1, rg), t = y - m * g;  // g > 0: y = t + g m
+            const unsigned iv = g ? I[(size_t)x * np + t * npg + m] : I[(size_t)y * np + x];
+            acc.add(res[y], inv_n2, iv);
+            res[y] = grad_rho(res[y], inv_n2, iv, rg_led);
+        }
+        __syncthreads();
+        res = stockham<false>(res, oth, 1, pl, tw, threadIdx.x, blockDim.x);
+        for (int j = threadIdx.x; j < nb; j += blockDim.x) T[(size_t)j * np + x] = res[j - r < 0 ? j - r + np : j - r];
+        res_block_partial<4>(acc, a, ((size_t)z * st.B + b) * a.nblk + x);
     } else if constexpr (kIsRes<A>) {
         const int g = st.meas_g;
         ResAcc<A> acc(rg_led);
@@ -451,6 +467,28 @@ __global__ void __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(E <= 16
             }
             pred_store(a, o + (size_t)y * np + c, pred_value(a, tile[idx], inv_n2, rg_led, iv));
         }
+    } else if constexpr (kIsGrad<A>) {
+        // fpm_gradient: the sums' walk below with rho written in place, then the
+        // step's tail (forward column transform, box rows back to T)
+        const int g = st.meas_g, npg = g ? np / g : 1;
+        const float rg = 1.0f / (float)(g ? g : 1);
+        ResAcc<A> acc(rg_led);
+        for (int idx = threadIdx.x; idx < np * C; idx += NT) {
+            const int y = idx >> lc, c = idx & cm;
+            if (c >= cs) continue;
+            const int m = udiv(y, g ? g : 1, rg), t = y - m * g;  // g > 0: y = t + g m
+            const unsigned iv = g ? I[(size_t)(x0 + c) * np + t * npg + m] : I[(size_t)y * np + x0 + c];
+            acc.add(tile[idx], inv_n2, iv);
+            tile[idx] = grad_rho(tile[idx], inv_n2, iv, rg_led);
+        }
+        __syncthreads();
+        tile_transform<false, NT, E>(tile, pl, lc, stw);
+        for (int idx = threadIdx.x; idx < nb * C; idx += NT) {
+            const int j = idx >> lc, c = idx & cm;
+            const int i = j - r < 0 ? j - r + np : j - r;
+            if (c < cs) T[(size_t)j * np + x0 + c] = tile[i * C + c];
+        }
+        res_block_partial<NT / 64>(acc, a, ((size_t)z * st.B + b) * a.nblk + blockIdx.x);
     } else if constexpr (kIsRes<A>) {
         // rows in natural order, the tile's C columns across adjacent lanes (no
         // LDS bank conflict).  The stack is read as C*2-byte row segments in
@@ -583,6 +621,30 @@ k_colpass_wave(DevState st, A a, FftPlan pl, const float2 *__restrict__ tw, int 
             }
             pred_store(a, o + (size_t)y * np + c, pred_value(a, smem[c * P + y], inv_n2, rg_led, iv1));
         }
+    } else if constexpr (kIsGrad<A>) {
+        // fpm_gradient: the sums and rho on the lane's own pixels, then the step's
+        // tail (wave-private forward transform, coalesced write-back of the box rows)
+        ResAcc<A> acc(rg_led);
+#pragma unroll
+        for (int q = 0; q < NQY; ++q) {
+            const int y = lane + 64 * q;
+#pragma unroll
+            for (int c = 0; c < CW; ++c) {
+                if (y >= np || w * CW + c >= cs) continue;
+                float2 *e = wb + c * P + y;
+                acc.add(*e, inv_n2, iv[q * CW + c]);
+                *e = grad_rho(*e, inv_n2, iv[q * CW + c], rg_led);
+            }
+        }
+        wave_sync();
+        wave_transform<false, LPC>(cb, pl, stw, l);
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < nb * C; idx += NT) {
+            const int j = udiv(idx, C, rC), c = idx - j * C;
+            const int i = j - r < 0 ? j - r + np : j - r;
+            if (c < cs) T[(size_t)j * np + x0 + c] = smem[c * P + i];
+        }
+        res_block_partial<NW>(acc, a, ((size_t)z * st.B + b) * a.nblk + blockIdx.x);
     } else if constexpr (kIsRes<A>) {
         ResAcc<A> acc(rg_led);
 #pragma unroll
@@ -672,7 +734,7 @@ LdsLadder plan_lds_ladder(const FftPlan &pl, int np, int nb, int B, const Switch
 // the ladder's K1 / K2 for the update step (A = StepArgs) or the sweep (ResArgs)
 template <class A>
 static void pick_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols) {
-    if constexpr (!kIsMom<A> && !kIsGainRes<A> && !kIsPred<A>) {  // the row kernels have no tail: every sweep launches the ResArgs ones
+    if constexpr (!kIsMom<A> && !kIsGainRes<A> && !kIsPred<A> && !kIsGrad<A>) {  // the row kernels have no tail: every sweep launches the ResArgs ones
         rows = l.rows;
         rows.fn = l.row_e == 16 ? (const void *)k_gather_rowifft_tiled<256, 16, A>
                   : l.row_e     ? (const void *)k_gather_rowifft_tiled<256, 24, A>
@@ -726,6 +788,12 @@ void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols
     pick_lds_kernels<MomArgs>(l, rows, cols_mom);
     pick_lds_kernels<PredArgs>(l, rows, cols_pred);
     pick_lds_kernels<ResArgs>(l, rows, cols);
+}
+
+// fpm_gradient's column kernel of the rung: the launch shape of the sweep's
+void gradient_lds_cols_kernel(const LdsLadder &l, StepKernel &cols_grad) {
+    StepKernel rows{};  // (untouched)
+    pick_lds_kernels<GradArgs>(l, rows, cols_grad);
 }
 
 hipError_t launch_general_step(const GeneralPlan &plan, const DevState &st, int led, int x0, int y0,

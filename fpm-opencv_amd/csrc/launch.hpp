@@ -140,7 +140,11 @@ struct ResArgs {
 //                C = sum |psi| sqrt(I) (null in a residual launch)
 //   PredArgs     fpm_predict: no sums at all, the tail stores every pixel of
 //                the image, out[entry - o0][patch][y][x] (perr .. nblk unused)
+//   GradArgs     fpm_gradient: the gained sums as GainResArgs', then rho in
+//                place of the amplitude replacement and the forward column
+//                transform, the box rows kept back in T (the step's tail)
 struct GainResArgs : ResArgs {};
+struct GradArgs : ResArgs {};
 struct MomArgs : ResArgs {
     double *pcross, *cross;
 };
@@ -158,6 +162,8 @@ struct ResidualPlan {
     StepKernel cols_gain;      // cols with the gained residual's tail and with the moments' (fpm_moments):
     StepKernel cols_mom;       //   the same launch shape
     StepKernel cols_pred;      // cols with the pixel-storing tail (fpm_predict): no fold follows it
+    StepKernel cols_grad;      // cols with fpm_gradient's tail (sums, rho, forward column transform)
+    StepKernel grad_rows;      // fpm_gradient's rows out (gradient.hip): one LED's grid, as rows
     LdsLadder ladder;         // Lds only: the rung rows / cols were picked from
     int nblk;                  // column blocks = partials per (LED, patch)
     int nl;                    // LEDs per launch
@@ -167,10 +173,11 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
                            const Switches &sw);
 // the sweep's kernels are the step's, instantiated for ResArgs: the ladder's
 // K1 / K2 (general.hip) and the Np 256 register column kernel (np256.hip)
-enum class ResTail { Plain, Gain, Moments, Predict };
+enum class ResTail { Plain, Gain, Moments, Predict, Grad };
 void residual_lds_kernels(const LdsLadder &l, StepKernel &rows, StepKernel &cols, StepKernel &cols_gain,
                           StepKernel &cols_mom, StepKernel &cols_pred);
 const void *residual_cols256_kernel(ResTail tail);
+void gradient_lds_cols_kernel(const LdsLadder &l, StepKernel &cols_grad);
 // rows, columns and fold of the nl entries ra.ent[ra.i0 ...] with the column
 // kernel of `tail` (Moments: ra.pcross / ra.cross set, both folds)
 hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, const MomArgs &ra, ResTail tail, int nl,
@@ -179,6 +186,27 @@ hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, cons
 // i's images go to pa.out's row i - pa.o0 (fpm_predict)
 hipError_t launch_predict_batch(const ResidualPlan &p, const DevState &st, const PredArgs &pa, int nl,
                                 const float2 *tw, hipStream_t s);
+
+// ---- fpm_gradient (gradient.hip)
+// What the rows-out and accumulate kernels of a batch need besides the sweep's
+// arguments: R [nl][B][nb][nb] scratch, the outputs (device memory, cleared
+// before the list's first batch; either null) and the bounding box, in the
+// centred spectrum, of the support boxes of the batch's windows.
+struct GradAcc {
+    const ResEntry *ent;  // set by the launcher from the batch: the list,
+    int i0, nl;           //   its first entry and the number of entries
+    const float2 *R;
+    float2 *gO;           // [B][L][L] un-centred (fpm_download's objF layout)
+    float2 *gP;           // [B][Np][Np] centred (fpm_download's pupil layout)
+    int bx0, by0, bw, bh;
+};
+// the rows-out launch for the plan's kind (called by plan_residual)
+void plan_gradient_rows(ResidualPlan &p, const DevState &st);
+// rows in, columns with the GradArgs tail and the fold of E / S (ra as
+// launch_residual_batch's), rows out, then the accumulation of the batch's nl
+// entries into acc.gO / acc.gP in list order
+hipError_t launch_gradient_batch(const ResidualPlan &p, const DevState &st, const MomArgs &ra, const GradAcc &acc,
+                                 int nl, const float2 *tw, hipStream_t s);
 
 // ---- batched transform of any length 2^a 3^b 5^c (fft_batch.hip)
 // Input band: sequences gs outside [qlo, qhi] and elements gi with

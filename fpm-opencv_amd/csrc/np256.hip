@@ -238,6 +238,27 @@ __global__ void __launch_bounds__(n256::NT) k_cols256(DevState st, A a, const fl
             const int row = g + GPB * k;
             pred_store(a, o + (size_t)row * N, pt[row * PP + t]);
         }
+    } else if constexpr (kIsGrad<A>) {
+        // fpm_gradient: the sums and rho = psi - g sqrt(I) psi / |psi| on the
+        // lane's pixels, then the step's tail (column DFT, box rows back to T)
+        const float inv_n2 = 1.0f / ((float)N * (float)N);
+        ResAcc<A> acc(rg_led);
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+            const unsigned iv = (iw[m >> 1] >> (16 * (m & 1))) & 0xffffu;
+            acc.add(y[m], inv_n2, iv);
+            y[m] = grad_rho(y[m], inv_n2, iv, rg_led);
+        }
+        dft256_full<false, true>(y, v, wt, LdsTw{twL, t, 1}, t, xrd);
+        __syncthreads();  // every group is done with its tile before the strip is rewritten
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+            const int j = boxrow(t + 16 * m, r);
+            if (j >= 0) strip[j * SP + g] = v[m];
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < tot; idx += NT) T[(size_t)(idx / GPB) * N + (idx % GPB)] = strip[(idx / GPB) * SP + (idx % GPB)];
+        res_block_partial<WPB>(acc, a, ((size_t)z * st.B + b) * a.nblk + sub);
     } else if constexpr (kIsRes<A>) {
         const float inv_n2 = 1.0f / ((float)N * (float)N);
         ResAcc<A> acc(rg_led);
@@ -402,7 +423,8 @@ __global__ void __launch_bounds__(n256::NT) __attribute__((amdgpu_waves_per_eu(4
 }  // namespace
 
 const void *residual_cols256_kernel(ResTail tail) {
-    return tail == ResTail::Predict ? (const void *)k_cols256<PredArgs>
+    return tail == ResTail::Grad ? (const void *)k_cols256<GradArgs>
+           : tail == ResTail::Predict ? (const void *)k_cols256<PredArgs>
            : tail == ResTail::Moments ? (const void *)k_cols256<MomArgs>
            : tail == ResTail::Gain  ? (const void *)k_cols256<GainResArgs>
                                     : (const void *)k_cols256<ResArgs>;

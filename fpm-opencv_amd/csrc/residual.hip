@@ -152,10 +152,13 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
         p.cols_gain.fn = residual_cols256_kernel(ResTail::Gain);
         p.cols_mom.fn = residual_cols256_kernel(ResTail::Moments);
         p.cols_pred.fn = residual_cols256_kernel(ResTail::Predict);
+        p.cols_grad = p.cols;
+        p.cols_grad.fn = residual_cols256_kernel(ResTail::Grad);
         p.nblk = kColBlocks;
     } else {
         p.ladder = plan_lds_ladder(pl, np, nb, B, sw, false);
         residual_lds_kernels(p.ladder, p.rows, p.cols, p.cols_gain, p.cols_mom, p.cols_pred);
+        gradient_lds_cols_kernel(p.ladder, p.cols_grad);
         p.nblk = (int)p.cols.grid.x;
     }
     // LEDs per launch: as many as the scratch cap holds (FPM_RES_BATCH=n forces n)
@@ -163,6 +166,7 @@ ResidualPlan plan_residual(const DevState &st, const FftPlan &pl, int n_order, i
     const size_t fit = kResidualScratchBytes / (p.t_led * sizeof(float2));
     p.nl = sw.res_batch > 0 ? sw.res_batch : (int)std::min<size_t>(std::max<size_t>(fit, 1), 65535);
     p.nl = std::max(1, std::min({p.nl, n_order, 65535}));
+    plan_gradient_rows(p, st);
     return p;
 }
 
@@ -170,7 +174,10 @@ hipError_t launch_residual_batch(const ResidualPlan &p, const DevState &st, cons
                                  const float2 *tw, hipStream_t s) {
     MomArgs ra = ra_in;
     ra.nblk = p.nblk;
-    const StepKernel *cols = tail == ResTail::Moments ? &p.cols_mom : tail == ResTail::Gain ? &p.cols_gain : &p.cols;
+    const StepKernel *cols = tail == ResTail::Moments ? &p.cols_mom
+                             : tail == ResTail::Gain  ? &p.cols_gain
+                             : tail == ResTail::Grad  ? &p.cols_grad
+                                                      : &p.cols;
     for (const StepKernel *k : {&p.rows, cols}) {
         // every instance but the moments' takes the ResArgs base (the leading bytes of ra)
         const bool mom = k == &p.cols_mom;

@@ -237,6 +237,15 @@ int predict(fpm_ctx *c, const fpm_probe *probes, int n, unsigned kind, bool dev,
 
 }  // namespace
 
+namespace fpm {
+int sweep_admit(fpm_ctx *c, const char *what) { return admit(c, what, true); }
+int sweep_resolve_probes(const fpm_ctx *c, const char *what, const fpm_probe *probes, int n,
+                         std::vector<ResEntry> &ent) {
+    return resolve_probes(c, what, probes, n, ent);
+}
+int sweep_ensure_scratch(fpm_ctx *c) { return ensure_scratch(c); }
+}  // namespace fpm
+
 extern "C" int fpm_predict(fpm_ctx *c, const fpm_probe *probes, int n, uint32_t flags, void *out,
                            double *elapsed_ms) {
     if (!c) return set_err(FPM_ERR_INVAL, "null ctx");

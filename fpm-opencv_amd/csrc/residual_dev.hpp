@@ -29,8 +29,13 @@ constexpr bool kIsGainRes = std::is_same<A, GainResArgs>::value;
 // stores every pixel (pred_value, pred_store below).
 template <class A>
 constexpr bool kIsPred = std::is_same<A, PredArgs>::value;
+// GradArgs (fpm_gradient) shares the front half and the gained sums, and goes
+// on where the sweep stops: its tail is the update step's shape (grad_rho below
+// in place of the amplitude replacement, then the forward column transform).
 template <class A>
-constexpr bool kIsRes = std::is_same<A, ResArgs>::value || kIsGainRes<A> || kIsMom<A> || kIsPred<A>;
+constexpr bool kIsGrad = std::is_same<A, GradArgs>::value;
+template <class A>
+constexpr bool kIsRes = std::is_same<A, ResArgs>::value || kIsGainRes<A> || kIsMom<A> || kIsPred<A> || kIsGrad<A>;
 
 // (|psi| - sqrt(I))^2 of one pixel added to acc: v = the unscaled IDFT value,
 // psi = v / Np^2 (the reference's ifft2 scaling), no eps.  I is exact and
@@ -69,7 +74,7 @@ __device__ __forceinline__ float res_add_gain(float acc, float2 v, float inv_n2,
 // at the update) or the moments.
 template <class A>
 __device__ __forceinline__ float res_gain(const DevState &st, int led, int b) {
-    if constexpr (kIsGainRes<A> || kIsPred<A>) return led_gain(st, led, b);
+    if constexpr (kIsGainRes<A> || kIsPred<A> || kIsGrad<A>) return led_gain(st, led, b);
     else return 1.0f;
 }
 
@@ -105,13 +110,27 @@ __device__ __forceinline__ void pred_store(const PredArgs &pa, size_t off, float
     else static_cast<float *>(pa.out)[off] = val;
 }
 
+// ---- fpm_gradient's tail: one pixel of rho = psi - g sqrt(I) psi / |psi|, the
+// residual field whose forward transform is the gradient's R (gradient.hip).
+// v = the unscaled IDFT value, psi = v / Np^2, no eps; written psi (a - s) / a
+// with a = |psi| as the sums form it and s = g sqrt(I) kept opaque as in
+// res_add_gain, so g = 1.0f gives the bits of no gain.  0 where |psi| = 0: a
+// window off the spectrum's support leaves rho exactly zero.
+__device__ __forceinline__ float2 grad_rho(float2 v, float inv_n2, unsigned I, float g) {
+    const float a = sqrtf(cabs2(v)) * inv_n2;
+    float s = g * sqrtf((float)I);
+    asm("" : "+v"(s));
+    const float f = a > 0.f ? (a - s) / a * inv_n2 : 0.f;
+    return make_float2(v.x * f, v.y * f);
+}
+
 template <class A>
 struct ResAcc {
     float e = 0.f, g, g2;
     unsigned s = 0;
     __device__ __forceinline__ explicit ResAcc(float gain) : g(gain), g2(gain * gain) {}
     __device__ __forceinline__ void add(float2 v, float inv_n2, unsigned I) {
-        if constexpr (kIsGainRes<A>) e = res_add_gain(e, v, inv_n2, I, g, g2);
+        if constexpr (kIsGainRes<A> || kIsGrad<A>) e = res_add_gain(e, v, inv_n2, I, g, g2);
         else e = res_add(e, v, inv_n2, I);
         s += I;
     }

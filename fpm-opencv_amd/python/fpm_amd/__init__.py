@@ -46,6 +46,7 @@ STITCH_ALIGN = {"none": 0, "phase": STITCH_ALIGN_PHASE, "complex": STITCH_ALIGN_
 # fpm_predict flags (fpm_hip.h FPM_PREDICT_*): one kind, optionally | PREDICT_DEVICE
 PREDICT_AMPLITUDE, PREDICT_COUNTS, PREDICT_DIFF, PREDICT_DEVICE = 0, 1, 2, 4
 PREDICT_KINDS = {"amplitude": PREDICT_AMPLITUDE, "counts": PREDICT_COUNTS, "diff": PREDICT_DIFF}
+GRAD_DEVICE = 1             # fpm_gradient: the gradients are device pointers (fpm_hip.h FPM_GRAD_DEVICE)
 # fpm_refocus flags (fpm_hip.h FPM_REFOCUS_*)
 REFOCUS_DEVICE = 1          # planes is a device pointer on the context's device
 REFOCUS_Z_PER_PATCH = 2     # zl is [nz][n_patch]
@@ -67,6 +68,7 @@ HIP_SYMBOLS = (
     "fpm_get_clock", "fpm_residual", "fpm_residual_at", "fpm_set_crops", "fpm_get_crops",
     "fpm_set_gains", "fpm_get_gains", "fpm_moments", "fpm_set_state", "fpm_download_state_device",
     "fpm_stitch_tiles", "fpm_stitch", "fpm_predict", "fpm_refocus",
+    "fpm_gradient",
 )
 # test-only entry points (include/fpm_hip_debug.h)
 HIP_DEBUG_SYMBOLS = ("fpm_debug_slot_update", "fpm_debug_update_coef", "fpm_debug_set_stall", "fpm_debug_get_plan",
@@ -207,6 +209,7 @@ def load_library(path: str = HIP_LIB):
         "fpm_get_gains": (C.c_int, [vp, f32p]),
         "fpm_moments": (C.c_int, [vp, C.POINTER(fpm_probe), C.c_int] + [C.POINTER(C.c_double)] * 4),
         "fpm_predict": (C.c_int, [vp, C.POINTER(fpm_probe), C.c_int, C.c_uint32, vp, C.POINTER(C.c_double)]),
+        "fpm_gradient": (C.c_int, [vp, C.POINTER(fpm_probe), C.c_int, C.c_uint32, vp, vp] + [C.POINTER(C.c_double)] * 3),
         "fpm_refocus": (C.c_int, [vp, C.POINTER(C.c_double), C.c_int, C.c_double, C.c_int, C.c_uint32, vp]
                         + [C.POINTER(C.c_double)] * 4),
         "fpm_set_state": (C.c_int, [vp, vp, vp, C.c_uint32]),
@@ -457,6 +460,49 @@ class Solver:
         ms = C.c_double()
         _check(_lib.fpm_predict(self._h, probes, n, flags, dst, C.byref(ms)))
         self.predict_ms = ms.value
+        return out
+
+    def gradient(self, pos=None, dx=None, dy=None, objF: bool = True, pupil: bool = True, sums: bool = False,
+                 device_ptrs=None):
+        """fpm_gradient: G = df/dRe + i df/dIm of the data-fidelity cost
+        f = sum E (residual()'s err, gains included) of the current state, so
+        that df = sum Re(conj(G) dz): PyTorch's convention, twice df/dconj(z).
+        Without pos the list is order[]; with pos / dx / dy it is residual_at's
+        entries (an LED may repeat; each entry counts once).  Returns a dict:
+        objF complex64 [n_patch][L][L] un-centred and pupil complex64
+        [n_patch][Np][Np] centred (download()'s layouts; exactly zero outside
+        the entries' disks / the support), each present when asked for; with
+        sums, err / ref float64 [n][n_patch] of the same pass.  device_ptrs =
+        (objF_ptr, pupil_ptr), either None / 0: device memory of the caller's
+        (float32 pairs) receives the gradients instead and the dict holds only
+        the sums.  The kernels' event time is left in gradient_ms.  Read-only,
+        blocking."""
+        p = self.prob
+        if pos is None:
+            if dx is not None or dy is not None:
+                raise ValueError("dx / dy without pos")
+            probes, n = None, len(p.order)
+        else:
+            probes, n = self._probes(pos, np.zeros_like(_i32(pos)) if dx is None else dx,
+                                     np.zeros_like(_i32(pos)) if dy is None else dy)
+        out, flags = {}, 0
+        if device_ptrs is not None:
+            po, pp = (C.c_void_p(q or 0) for q in device_ptrs)
+            flags = GRAD_DEVICE
+        else:
+            if objF:
+                out["objF"] = np.empty((p.n_patch, p.L, p.L), np.complex64)
+            if pupil:
+                out["pupil"] = np.empty((p.n_patch, p.np_, p.np_), np.complex64)
+            po, pp = (out[k].ctypes.data_as(C.c_void_p) if k in out else None for k in ("objF", "pupil"))
+        dp = C.POINTER(C.c_double)
+        if sums:
+            out["err"] = np.empty((n, p.n_patch), np.float64)
+            out["ref"] = np.empty_like(out["err"])
+        ms = C.c_double()
+        _check(_lib.fpm_gradient(self._h, probes, n, flags, po, pp, out["err"].ctypes.data_as(dp) if sums else None,
+                                 out["ref"].ctypes.data_as(dp) if sums else None, C.byref(ms)))
+        self.gradient_ms = ms.value
         return out
 
     def refocus(self, zl, fl: float, margin: int = 0, planes: bool = True, device_ptr: int | None = None,

@@ -42,10 +42,12 @@ extern "C" {
  * FPM_HAS_STATE = fpm_set_state, fpm_download_state_device;
  * FPM_HAS_STITCH = fpm_stitch_tiles, fpm_stitch;
  * FPM_HAS_PREDICT = fpm_predict;
- * FPM_HAS_REFOCUS = fpm_refocus. */
+ * FPM_HAS_REFOCUS = fpm_refocus;
+ * FPM_HAS_GRADIENT = fpm_gradient. */
 #define FPM_ABI_VERSION   6
 #define FPM_HAS_PREDICT 1
 #define FPM_HAS_REFOCUS 1
+#define FPM_HAS_GRADIENT 1
 #define FPM_HAS_LED_CALIBRATION 1
 #define FPM_HAS_LED_GAINS 1
 #define FPM_HAS_STATE 1
@@ -344,6 +346,60 @@ int  fpm_moments(fpm_ctx *ctx, const fpm_probe *probes, int n, double *model, do
 #define FPM_PREDICT_DEVICE    4u
 int  fpm_predict(fpm_ctx *ctx, const fpm_probe *probes, int n, uint32_t flags, void *out,
                  double *elapsed_ms);
+
+/* The gradient of the data-fidelity cost of the current state.  For a list of
+ * entries and every patch, with psi exactly as fpm_residual's,
+ *   psi_i = ifft2(ifftshift(W_i) P)       scaled 1/Np^2, no eps
+ *   W_i   = the entry's Np x Np window of O = fftshift(objF)
+ *   P     = ifftshift(pupil support)
+ *   f     = sum_i sum_yx (|psi_i| - g_i sqrt(I_i))^2 = sum_i E_i of fpm_residual_at
+ * the outputs are G = df/dRe(z) + i df/dIm(z), so that df = sum Re(conj(G) dz):
+ * the convention of PyTorch's complex leaves, twice the Wirtinger derivative
+ * df/dconj(z).  With
+ *   rho_i = psi_i - g_i sqrt(I_i) psi_i / |psi_i|    (0 where |psi_i| = 0)
+ *   R_i   = fft2(rho_i) / Np^2
+ *   G_O[window_i] += 2 fftshift(conj(P) R_i)        grad_objF  = ifftshift(G_O)
+ *   G_P           += 2 conj(ifftshift(W_i)) R_i     grad_pupil = fftshift(G_P) support
+ *   grad_objF  [n_patch][L][L][2]    un-centred, fpm_download's objF layout
+ *   grad_pupil [n_patch][Np][Np][2]  centred, fpm_download's pupil layout
+ *   err, ref   [n][n_patch]          E and S of the same entries (fpm_residual_at's),
+ *                                    from the same pass; either may be NULL
+ * The gradients are host memory, or with FPM_GRAD_DEVICE memory of the
+ * context's device; either may be NULL, not both.  They are fp32 on every
+ * context (FPM_FLAG_SPEC_FP16 included).
+ * probes == NULL: the context's own list (n is ignored), as fpm_predict;
+ * otherwise fpm_residual_at's entries, validation, messages and row order: a
+ * moved window gives the gradient with that window, and a list may name an LED
+ * more than once (each entry counts once).
+ * Every element of an output is written: exactly zero outside the union of the
+ * entries' support disks (grad_objF) and outside the support (grad_pupil).  An
+ * entry whose window misses the spectrum's support (psi = 0) adds exactly
+ * nothing.  A gain table of ones returns the bits of no table.
+ * Deterministic without floating-point atomics: entries are added in list
+ * order, each element by one thread, so the bits depend on the state and the
+ * list alone -- not on FPM_RES_BATCH, on how the list was cut into launches or
+ * on an earlier call.
+ * One use: objF -= Np^2 grad_objF / (2 M), M_k = sum_i |P(k - c_i)|^2 (c_i the
+ * window's position) where M > 0, majorises the cost: with the pupil held fixed
+ * it never increases f.  The same holds for the pupil with the object fixed
+ * and M_k = sum_i |O(c_i + k)|^2.  A spectrum given to fpm_set_state must stay
+ * zero outside the live band; the gradient of the context's own list is.
+ * The contract of fpm_predict: read-only (spectrum, pupil, maxima, objCrop,
+ * stack, gains, crops, fpm_timing and fpm_clock are left bit for bit),
+ * blocking; FPM_ERR_INVAL on a capturing stream before anything is enqueued, on
+ * an unknown flag bit and on both gradient pointers NULL; FPM_ERR_STATE before
+ * a state exists or with no stack uploaded.
+ * It runs the residual sweep's kernels and scratch plus R of one launch's
+ * entries (nl n_patch (2r+1)^2 complex), allocated by the first call; a host
+ * output goes through a device copy of its own size, allocated by the first
+ * call that asks for it; with a device pointer the accumulation goes straight
+ * into the caller's memory.  All of it is counted in fpm_info.device_bytes.
+ * elapsed_ms (may be NULL): event to event over the kernels; the copies of the
+ * gradients to the host are outside it. */
+#define FPM_GRAD_DEVICE 1u   /* grad_objF / grad_pupil are memory of the context's device */
+int  fpm_gradient(fpm_ctx *ctx, const fpm_probe *probes, int n, uint32_t flags,
+                  float *grad_objF, float *grad_pupil, double *err, double *ref,
+                  double *elapsed_ms);
 
 /* Digital refocusing: the recovered field propagated to other z planes by the
  * angular-spectrum method, and the sums a focus measure is made of, without
